@@ -14,6 +14,11 @@ HBM before the timed region).  Multi-GPU: one process per GPU, rows sharded
 torch.distributed.run with N ranks (a child process, started before anything
 touches the GPU); the driver's own torchrun launch takes the same path.
 
+A plain run sets up, warms up, times `--steps` steps, writes the last step's
+scores with `--dump-outputs DIR`, and prints the result line.  `--full` adds
+what takes runs of its own: the measured roofline ceilings and PMC traffic,
+the CPU baseline with the K1 parity check, and the C3 / C4 / C5 / HR@10 legs.
+
 Prints ONE JSON line (rank 0).  See DESIGN.md §Measurement.
 """
 from __future__ import annotations
@@ -69,6 +74,15 @@ def parse():
     p.add_argument("--c5-rows", type=int, default=12_500_000)
     p.add_argument("--no-check", action="store_true",
                    help="skip the legs' oracle parity checks (timing only)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline steps also run everything else the benchmark "
+                        "measures or checks: the measured HBM ceilings and the PMC traffic "
+                        "passes of the roofline, the CPU baseline with its parity check, and "
+                        "the extra legs (--legs); a plain run times the headline steps only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed to "
+                        "DIR/<name>.npy (float32; a fixed seeded sample when the output is "
+                        "larger than the dump budget)")
     p.add_argument("--dry-run", action="store_true",
                    help="launcher check without a GPU: every rank joins a gloo group and "
                         "rank 0 prints the world it saw")
@@ -793,6 +807,75 @@ def gather_rows_peak(idx, E, reps=5):
     return bpr * idx.shape[0] / (best * 1e-3) / 1e9, best
 
 
+def measured_roofline(args, rank, world, idx, E, kern_ms, achieved, bpr_lines):
+    """--full: the roofline entries that take runs of their own: the measured
+    stream-read and gather ceilings and K1's HBM traffic from the PMC passes
+    (or the committed calibration when they cannot run)."""
+    peak_meas, peak_variants = stream_read_peak(E)
+    gather_peak, gather_ms = gather_rows_peak(idx, E)
+    traffic, pmc, why = None, None, "--no-pmc"
+    if rank == 0 and world == 1 and not args.no_pmc:
+        pmc, why = pmc_traffic(args.rows, args.k)
+    if pmc is not None:
+        # PMC bytes per row of this run (corrected FETCH_SIZE + WRITE_SIZE) x rows per launch
+        traffic = pmc["hbm_bytes_per_row"] * args.rows
+        traffic_source = ("measured in this run: rocprofv3 --pmc FETCH_SIZE and WRITE_SIZE "
+                          "passes (child processes) over scripts/pmc_fm_rows.py at "
+                          f"{args.rows} rows, FETCH_SIZE calibrated on a known-byte launch")
+    elif os.path.exists(args.traffic_json):
+        traffic_source = (f"calibrated, not measured in this run ({why}): PMC bytes/row from "
+                          f"{os.path.relpath(args.traffic_json, ROOT)} x rows")
+        try:
+            with open(args.traffic_json) as f:
+                tj = json.load(f)
+            if tj.get("k") == args.k and tj.get("fields") == 5:
+                traffic = tj["hbm_bytes_per_row"] * args.rows
+        except (OSError, ValueError):
+            traffic = None
+    else:
+        traffic_source = f"none ({why})"
+    return {"traffic": traffic,
+            "traffic_GBps": (traffic / (kern_ms * 1e-3) / 1e9) if traffic else None,
+            "traffic_frac": (traffic / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
+                            if traffic else None,
+            "peak_measured": peak_meas,
+            "peak_measured_how": "hhfm_probe_stream_read: one 16-B/lane read of the "
+                                 "4.3 GB table, best variant and launch of 5, this box",
+            "peak_measured_variants": peak_variants,
+            "frac_vs_measured": (achieved / peak_meas) if peak_meas else None,
+            "peak_gather_measured": gather_peak,
+            "peak_gather_how": "the same row kernel over the same rows' user and item "
+                               "columns only (2 random 256-B rows, no w / context "
+                               f"loads): {gather_ms:.3f} ms, best of 5, this box",
+            "frac_vs_gather": achieved / gather_peak,
+            "line_frac_vs_measured": (bpr_lines * args.rows / (kern_ms * 1e-3) / 1e9
+                                      / peak_meas) if peak_meas else None,
+            "traffic_source": traffic_source,
+            "traffic_pmc": pmc}
+
+
+DUMP_BUDGET_BYTES = 32 << 20      # all ranks together, well under 64 MB
+DUMP_SEED = 20240
+
+
+def dump_outputs(path, out, rank, world):
+    """--dump-outputs: the scores the last timed hhfm_fm_score_rows launch
+    wrote (what a caller of ops.fm_score_rows receives), one float32 file per
+    rank.  An output above this rank's share of the budget is sampled at
+    sorted row positions drawn without replacement from a fixed seed, so two
+    builds run with the same arguments write the same rows."""
+    os.makedirs(path, exist_ok=True)
+    n = out.shape[0]
+    keep = DUMP_BUDGET_BYTES // 4 // world
+    if n > keep:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+        vals = out[torch.from_numpy(pos).to(out.device)]
+    else:
+        vals = out
+    name = "fm_score_rows" if world == 1 else f"fm_score_rows_rank{rank}"
+    np.save(os.path.join(path, name + ".npy"), vals.cpu().numpy().astype(np.float32))
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -855,29 +938,11 @@ def main():
     # that cross HBM at that granularity are 2 rows x 256 B + 2 w lines x 128 B
     # + ids + out = 792 B/row at k=64.
     bpr_lines = 2 * args.k * 4 + 2 * 128 + 5 * 4 + 4
-    peak_meas, peak_variants = stream_read_peak(E)
-    gather_peak, gather_ms = gather_rows_peak(idx, E)
-    traffic, pmc, why = None, None, "--no-pmc"
-    if rank == 0 and world == 1 and not args.no_pmc:
-        pmc, why = pmc_traffic(args.rows, args.k)
-    if pmc is not None:
-        # PMC bytes per row of this run (corrected FETCH_SIZE + WRITE_SIZE) x rows per launch
-        traffic = pmc["hbm_bytes_per_row"] * args.rows
-        traffic_source = ("measured in this run: rocprofv3 --pmc FETCH_SIZE and WRITE_SIZE "
-                          "passes (child processes) over scripts/pmc_fm_rows.py at "
-                          f"{args.rows} rows, FETCH_SIZE calibrated on a known-byte launch")
-    elif os.path.exists(args.traffic_json):
-        traffic_source = (f"calibrated, not measured in this run ({why}): PMC bytes/row from "
-                          f"{os.path.relpath(args.traffic_json, ROOT)} x rows")
-        try:
-            with open(args.traffic_json) as f:
-                tj = json.load(f)
-            if tj.get("k") == args.k and tj.get("fields") == 5:
-                traffic = tj["hbm_bytes_per_row"] * args.rows
-        except (OSError, ValueError):
-            traffic = None
-    else:
-        traffic_source = f"none ({why})"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
+    measured = {}
+    if args.full:
+        measured = measured_roofline(args, rank, world, idx, E, kern_ms, achieved, bpr_lines)
 
     result = {
         "metric": METRIC, "value": value, "unit": "triples/s", "n_gpus": world,
@@ -892,31 +957,22 @@ def main():
                    "table_rows": M, "table_bytes": M * args.k * 4,
                    "parallelism": f"rows sharded x{world}, no collective"},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                      "kernel": "fm_rows_fast<5,16,f32,w,NTM 2>", "kernel_ms": kern_ms,
-                     "traffic_GBps": (traffic / (kern_ms * 1e-3) / 1e9) if traffic else None,
-                     "traffic_frac": (traffic / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
-                                     if traffic else None,
                      "algorithmic_bytes_per_row": bpr,
                      "survey_bytes_per_row": bpr_survey,
                      "survey_rate_GBps": bpr_survey * args.rows / (kern_ms * 1e-3) / 1e9,
-                     "peak_measured": peak_meas,
-                     "peak_measured_how": "hhfm_probe_stream_read: one 16-B/lane read of the "
-                                          "4.3 GB table, best variant and launch of 5, this box",
-                     "peak_measured_variants": peak_variants,
-                     "frac_vs_measured": (achieved / peak_meas) if peak_meas else None,
-                     "peak_gather_measured": gather_peak,
-                     "peak_gather_how": "the same row kernel over the same rows' user and item "
-                                        "columns only (2 random 256-B rows, no w / context "
-                                        f"loads): {gather_ms:.3f} ms, best of 5, this box",
-                     "frac_vs_gather": achieved / gather_peak,
                      "line_bytes_per_row": bpr_lines,
-                     "line_rate_GBps": bpr_lines * args.rows / (kern_ms * 1e-3) / 1e9,
-                     "line_frac_vs_measured": (bpr_lines * args.rows / (kern_ms * 1e-3) / 1e9
-                                               / peak_meas) if peak_meas else None,
-                     "traffic_source": traffic_source,
-                     "traffic_pmc": pmc},
+                     "line_rate_GBps": bpr_lines * args.rows / (kern_ms * 1e-3) / 1e9},
     }
+    if not args.full:
+        # a plain run: the headline steps only (everything below takes runs of its own)
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
+    result["roofline"].update(measured)
     if rank == 0 and world == 1 and args.cpu_seconds > 0:
         result["cpu_baseline"] = cpu_baseline(idx, E, w, w0, out, args)
     legs = [x for x in args.legs.split(",") if x]

@@ -15,7 +15,7 @@ for n in base "$@"; do
 done
 for n in "$@"; do python scripts/diag/wide_compare.py $o/base.npz $o/$n.npz; done
 for rep in 1 2; do for n in base "$@"; do
-  HHFM_AB_ROOT=/tmp/wv_$n timeout -k 10 300 python bench.py --legs c5 --no-pmc > $o/c5_$n.json 2> $o/c5_$n.err || { tail -20 $o/c5_$n.err; exit 1; }
+  HHFM_AB_ROOT=/tmp/wv_$n timeout -k 10 300 python bench.py --full --legs c5 --no-pmc > $o/c5_$n.json 2> $o/c5_$n.err || { tail -20 $o/c5_$n.err; exit 1; }
   python3 -c "
 import json
 d = json.loads(open('$o/c5_$n.json').read().strip().splitlines()[-1]); ex = d.get('extra', d)

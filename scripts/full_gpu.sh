@@ -11,7 +11,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout
 tail -1 $out/pytest.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || { echo "smoke failed"; tail $out/smoke.log; exit 1; }
 cat $out/smoke.log
-timeout -k 10 400 python bench.py > $out/bench.json 2> $out/bench.err || { echo "bench failed"; tail $out/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $out/bench.json 2> $out/bench.err || { echo "bench failed"; tail $out/bench.err; exit 1; }
 cat $out/bench.json
 bash scripts/gpu_profile.sh > $out/profile.log 2>&1 || { echo "profile failed"; tail $out/profile.log; exit 1; }
 echo "profiles done"

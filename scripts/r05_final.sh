@@ -10,8 +10,8 @@ mkdir -p $o
 HHFM_PARITY_REPORT=$o/parity_report.json timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 200 --timeout-method thread > $o/pytest_gpu.txt 2>&1 || { echo "pytest failed"; tail -30 $o/pytest_gpu.txt; exit 1; }
 tail -2 $o/pytest_gpu.txt
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $o/smoke.txt 2>&1 || { echo "smoke failed"; tail $o/smoke.txt; exit 1; }
-timeout -k 10 500 python bench.py > $o/bench_full.json 2> $o/bench_full.err || { echo "bench failed"; tail $o/bench_full.err; exit 1; }
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $o/trace -o bench --output-format csv -- python3 bench.py --steps 20 --warmup 3 --cpu-seconds 0 --no-pmc > $o/bench_under_rocprof.json 2> $o/trace.err || { echo "trace failed"; tail $o/trace.err; exit 1; }
+timeout -k 10 500 python bench.py --full > $o/bench_full.json 2> $o/bench_full.err || { echo "bench failed"; tail $o/bench_full.err; exit 1; }
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $o/trace -o bench --output-format csv -- python3 bench.py --full --steps 20 --warmup 3 --cpu-seconds 0 --no-pmc > $o/bench_under_rocprof.json 2> $o/trace.err || { echo "trace failed"; tail $o/trace.err; exit 1; }
 python3 scripts/timed_stats.py $(find $o/trace -name 'bench_kernel_trace.csv' | head -1) 3 20 $o/bench_kernel_stats_timed.csv || { echo "timed stats failed"; exit 1; }
 timeout -k 10 600 python scripts/rowtable.py > $o/rows.json 2> $o/rows.err || { echo "rowtable failed"; tail $o/rows.err; exit 1; }
 echo done

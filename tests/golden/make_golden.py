@@ -22,6 +22,9 @@ Frappe README forbids redistribution):
   epoch_stream.json     the batches the reference's own Train.train feeds
                         partial_fit (FM and OurModel7, 2 epochs on
                         synth_frappe, seeded): per-batch sha256 of X/Y/F1
+  frappe_shape.json     LoadData split hashes and evaluate_TopK HR/NDCG/PRE@5/@10
+                        on bench.frappe_shape_dataset's 96,203-row file
+                        (`make_golden.py frappe_shape` writes this one alone)
 Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
 """
 from __future__ import annotations
@@ -441,17 +444,24 @@ def gen_epoch_stream():
     print("epoch_stream", {k: len(v) for k, v in res.items() if isinstance(v, list)})
 
 
-def gen_frappe_real():
-    """Real Frappe (builder container only): commit only derived numbers —
-    split hashes and the reference harness's HR/NDCG/PRE@10 for a seeded
-    random-weight HHFM scored by the oracle (no rows are redistributed)."""
+def gen_frappe_shape():
+    """Frappe at scale without Frappe's rows (its README forbids
+    redistribution): bench.frappe_shape_dataset writes a seeded libfm file of
+    Frappe's shape (957 users, 4,082 items, ctx 7/2/3, 96,203 rows); recorded
+    are the reference loader's sizes and split hashes on it and the reference
+    harness's HR/NDCG/PRE@5/@10 for a seeded random-weight HHFM scored by the
+    oracle, with the file's own sha256."""
     import hashlib
-    path = os.path.join(REF, "data", "positive") + "/"
-    if not os.path.exists(path + "frappe/frappe.libfm"):
-        return
-    np.random.seed(2016)
-    d = NLD.LoadData(path, "frappe")
-    res = {"sizes": [d.n_user, d.n_item, d.features_M],
+    import tempfile
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    import bench
+    with tempfile.TemporaryDirectory() as tmp:
+        path = bench.frappe_shape_dataset(tmp)
+        with open(os.path.join(path, "frappe_shape", "frappe_shape.libfm"), "rb") as f:
+            file_sha = hashlib.sha256(f.read()).hexdigest()
+        np.random.seed(2016)
+        d = NLD.LoadData(path, "frappe_shape")
+    res = {"file_sha256": file_sha, "sizes": [d.n_user, d.n_item, d.features_M],
            "train_sha256": hashlib.sha256(np.ascontiguousarray(d.Train_data.values, np.int64)).hexdigest(),
            "test_sha256": hashlib.sha256(np.ascontiguousarray(d.Test_data.values, np.int64)).hexdigest()}
     E = np.random.default_rng(606).normal(0, 0.01, (d.features_M, 64)).astype(np.float32)
@@ -461,9 +471,9 @@ def gen_frappe_real():
         t.data, t.n_user, t.n_item, t.TopK, t.model = d, d.n_user, d.n_item, topk, model
         np.random.seed(31)
         res[f"hhfm_random_w_topk{topk}"] = [float(x) for x in t.evaluate_TopK(d.Test_data)]
-    with open(os.path.join(HERE, "frappe_real.json"), "w") as f:
+    with open(os.path.join(HERE, "frappe_shape.json"), "w") as f:
         json.dump(res, f, indent=1, sort_keys=True)
-    print("frappe_real", res)
+    print("frappe_shape", res)
 
 
 def main():
@@ -482,8 +492,11 @@ def main():
     gen_losses()
     gen_harness(d)
     gen_epoch_stream()
-    gen_frappe_real()
+    gen_frappe_shape()
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["frappe_shape"]:     # that fixture alone
+        gen_frappe_shape()
+    else:
+        main()

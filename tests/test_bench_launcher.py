@@ -34,6 +34,26 @@ def test_bench_gpus_1_stays_single_process():
     assert d["world"] == 1 and d["ranks"] == [0]
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.dump_outputs: an output within the budget is written whole, a
+    larger one as the same seeded sorted sample every time; float32 files,
+    one per rank."""
+    import numpy as np
+    import torch
+    import bench
+    out = torch.arange(1000, dtype=torch.float32) * 0.5
+    bench.dump_outputs(str(tmp_path / "a"), out, 0, 1)
+    a = np.load(tmp_path / "a" / "fm_score_rows.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, out.numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 300)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), out, 1, 2)
+    b = np.load(tmp_path / "b" / "fm_score_rows_rank1.npy")
+    assert b.dtype == np.float32 and b.shape == (150,)
+    assert np.all(np.diff(b) > 0) and np.isin(b, out.numpy()).all()
+    assert np.array_equal(b, np.load(tmp_path / "c" / "fm_score_rows_rank1.npy"))
+
+
 def test_pmc_bytes_per_row_calibration():
     """bench.pmc_bytes_per_row: FETCH_SIZE scaled so the calibration launch
     reads its known bytes; WRITE_SIZE taken as is."""

@@ -51,6 +51,39 @@ def test_c4_shards_merge_to_the_unsharded_top20():
     assert res[1] == res[2] == res[3], res
 
 
+def test_plain_run_dumps_the_last_steps_scores(tmp_path):
+    """A plain `bench.py --steps K --warmup W --dump-outputs DIR` (a child
+    process) prints the headline line without the --full sections, and the
+    dumped float32 scores are what ops.fm_score_rows gives on the same seeded
+    batch in this process, bit for bit (same inputs from run to run)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from hhfm_amd import ops
+    rows, nu, ni = 70_001, 3000, 5000
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(bench.__file__), "bench.py"),
+                        "--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", str(rows),
+                        "--users", str(nu), "--items", str(ni), "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["unit"] == "triples/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["metric"] == bench.METRIC
+    assert abs(d["value"] - rows / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    for key in ("cpu_baseline", "extra", "parity"):
+        assert key not in d
+    assert "peak_measured" not in d["roofline"]
+    assert os.listdir(tmp_path) == ["fm_score_rows.npy"]
+    got = np.load(tmp_path / "fm_score_rows.npy")
+    assert got.dtype == np.float32 and got.shape == (rows,)
+    dev = torch.device("cuda", 0)
+    idx, E, w, _ = bench.make_batch(rows, nu, ni, 64, 1, dev)
+    assert np.array_equal(got, ops.fm_score_rows(idx, E, w, 0.0).cpu().numpy())
+
+
 def test_stream_read_probe_and_c5_leg_run():
     dev = torch.device("cuda", 0)
     buf = torch.empty(1 << 28, dtype=torch.uint8, device=dev)

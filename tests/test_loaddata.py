@@ -49,35 +49,40 @@ def test_loaddata_shared_token_ids():
     assert "night" in set(raw[3]) and "night" in set(raw[5])
 
 
-REAL = "/root/reference/data/positive/"
+@pytest.fixture(scope="module")
+def frappe_shape(tmp_path_factory):
+    """bench.frappe_shape_dataset's seeded libfm file (Frappe's shape and
+    size, none of its rows; Frappe itself may not be redistributed) and the
+    reference's results on it (tests/golden/make_golden.py gen_frappe_shape)."""
+    import bench
+    path = bench.frappe_shape_dataset(str(tmp_path_factory.mktemp("frappe_shape")))
+    with open(os.path.join(G, "frappe_shape.json")) as f:
+        ref = json.load(f)
+    with open(os.path.join(path, "frappe_shape", "frappe_shape.libfm"), "rb") as f:
+        assert hashlib.sha256(f.read()).hexdigest() == ref["file_sha256"]
+    return path, ref
 
 
 @pytest.mark.parametrize("encoder", ["native", "python"])
-@pytest.mark.skipif(not os.path.exists(REAL + "frappe/frappe.libfm"),
-                    reason="real Frappe only exists in the builder container")
-def test_loaddata_real_frappe_hashes(encoder):
-    with open(os.path.join(G, "frappe_real.json")) as f:
-        ref = json.load(f)
+def test_loaddata_frappe_shape_hashes(frappe_shape, encoder):
+    path, ref = frappe_shape
     np.random.seed(2016)
-    d = LoadData(REAL, "frappe", encoder=encoder)
+    d = LoadData(path, "frappe_shape", encoder=encoder)
     assert [d.n_user, d.n_item, d.features_M] == ref["sizes"]
     assert hashlib.sha256(np.ascontiguousarray(d.Train_data.values, np.int64)).hexdigest() == ref["train_sha256"]
     assert hashlib.sha256(np.ascontiguousarray(d.Test_data.values, np.int64)).hexdigest() == ref["test_sha256"]
 
 
-@pytest.mark.skipif(not os.path.exists(REAL + "frappe/frappe.libfm"),
-                    reason="real Frappe only exists in the builder container")
-def test_hr_at_k_real_frappe_matches_reference_harness():
+def test_hr_at_k_frappe_shape_matches_reference_harness(frappe_shape):
     """Same loader split + same sampled rows + same top-20 lists => the same
-    HR/NDCG/PRE@K as the reference harness on real Frappe (model: seeded
-    random-weight HHFM scored by the oracle; trained reference weights do
-    not exist)."""
+    HR/NDCG/PRE@K as the reference harness on the Frappe-shape file (model:
+    seeded random-weight HHFM scored by the oracle; trained reference weights
+    do not exist)."""
     from hhfm_amd.OurModel7 import Train as M7Train
     from tests.test_harness import OracleModel
-    with open(os.path.join(G, "frappe_real.json")) as f:
-        ref = json.load(f)
+    path, ref = frappe_shape
     np.random.seed(2016)
-    d = LoadData(REAL, "frappe")
+    d = LoadData(path, "frappe_shape")
     E = np.random.default_rng(606).normal(0, 0.01, (d.features_M, 64)).astype(np.float32)
     m = OracleModel(E, None, d.n_user, d.n_item, fm_scores=False)
     for topk in (5, 10):

@@ -170,6 +170,264 @@ __global__ __launch_bounds__(256) void fm_rows_fast(
   report_bad_id(status, bad);
 }
 
+// ---------------------------------------------------------------------------
+// FM row kernel for 3 <= F <= 8 with the table's tail served from LDS
+// (DESIGN.md §K1 "hot tail"; the kernel the issue calls fm_rows_hot — the name
+// keeps the fm_rows_fast prefix the benchmark's PMC passes select rows by).
+//
+// The loaders number tokens column-major (users, items, then each context
+// column: NewLoadData.py), so the small-vocabulary columns' rows are the last
+// rows of the table.  Every workgroup stages the last T = 16 KiB / row_bytes
+// rows (and their `w`) in LDS once; a wave-iteration whose field-2.. ids all
+// lie in that window keeps only the user and item rows in registers across
+// the HBM wait and reads the others from LDS when it consumes them: 2 x U row
+// loads per lane in flight in the register budget of 3 waves per SIMD, where
+// fm_rows_fast<5> holds F x U = 25 at 2 waves.
+//
+// Any input is served: the first wave-iteration with an id outside the window
+// (a clamped bad id included, unless the whole table is in the window) sends
+// its wave to the general loop below — every field from global memory, UG row
+// slots — for that iteration and the rest of its rows.  Same per-element
+// order, same lane-to-field assignment of `w`, same (t + fb) + w0 as
+// fm_rows_fast: the same bits on either path.
+// ---------------------------------------------------------------------------
+#ifndef HHFM_K1_HOT_U
+#define HHFM_K1_HOT_U 6   // row slots per lane of the LDS-tail loop
+#endif
+#ifndef HHFM_K1_HOT_CAP
+#define HHFM_K1_HOT_CAP HHFM_K1_CAP   // blocks per CU (each stages 16 KiB)
+#endif
+#ifndef HHFM_K1_HOT_AUTO
+#define HHFM_K1_HOT_AUTO 1   // 0: only HHFM_FLAG_HOT_TAIL selects the kernel
+#endif
+constexpr int kHotWindowBytes = 16384;
+
+// Row slots of the two loops, sized so that the kernel stays within the 168
+// VGPRs of 3 waves per SIMD (profiles/k1_hot_tail_resources.txt; the bf16
+// F = 8 and two bf16 F = 6 variants do not, and run at fm_rows_fast's 2 waves)
+template <int F>
+struct HotRows {
+  static constexpr int U = F <= 6 ? HHFM_K1_HOT_U : 4;  // LDS-tail loop (2 rows per slot)
+  static constexpr int UG = F <= 5 ? 3 : 2;             // general loop (F rows per slot)
+};
+
+// rows of wave-iteration `base`, slots u0 .. u0+UG-1 (slots >= U and rows
+// >= B read row 0: unconditional loads keep the vmcnt counting exact)
+template <int F, int U, int UG>
+HHFM_DEV void load_ids_slots(int32_t (&id)[UG][F], const int32_t* __restrict__ idx,
+                             int64_t base, int u0, int64_t B, int g, int RPW) {
+#pragma unroll
+  for (int u = 0; u < UG; ++u) {
+    int64_t row = base + (int64_t)(u0 + u) * RPW + g;
+    const int32_t* p = idx + ((u0 + u < U && row < B) ? row : 0) * (int64_t)F;
+#pragma unroll
+    for (int f = 0; f < F; ++f) id[u][f] = p[f];
+  }
+}
+
+// Σ_e ½((Σ_f c_f)² − Σ_f c_f²) of one lane's chunk, fields in index order
+template <int F, typename C>
+HHFM_DEV float fm_chunk_term(const C (&c)[F]) {
+  float t = 0.f;
+#pragma unroll
+  for (int e = 0; e < C::kElems; ++e) {
+    float s = c[0].v[e];
+    float q = c[0].v[e] * c[0].v[e];
+#pragma unroll
+    for (int f = 1; f < F; ++f) {
+      s += c[f].v[e];
+      q += c[f].v[e] * c[f].v[e];
+    }
+    t += 0.5f * (s * s - q);
+  }
+  return t;
+}
+
+template <int F, int LPR, bool BF16, bool HAS_W, bool NT01>
+__global__ __launch_bounds__(256) void fm_rows_fast_hot(
+    const int32_t* __restrict__ idx, int64_t B, const char* __restrict__ E,
+    int64_t M, const float* __restrict__ w, float w0, float* __restrict__ out,
+    int32_t* __restrict__ status) {
+  static_assert(F >= 3 && F <= 10 && LPR >= 4, "fields 2.. pack into 8-bit local indices");
+  constexpr int U = HotRows<F>::U;
+  constexpr int UG = HotRows<F>::UG;
+  constexpr int RPW = kWave / LPR;
+  constexpr int RPI = RPW * U;
+  constexpr int64_t ROW_BYTES = (int64_t)LPR * 16;
+  constexpr int T = kHotWindowBytes / (int)ROW_BYTES;  // window rows (<= 256)
+  constexpr int NC = F - 2;                            // fields read from LDS
+  constexpr int PKW = (NC + 3) / 4;                    // 4 local indices per register
+  constexpr int WPL = (F + LPR - 1) / LPR;
+  static_assert(T <= 256, "local index is 8 bits");
+  using C = Chunk<BF16>;
+
+  __shared__ u32x4_t hot[T * LPR];
+  __shared__ float hotw[HAS_W ? T : 1];
+
+  // window [ws, M): the table's last T rows, clipped to the table
+  const int64_t ws = M > T ? M - T : 0;
+  const int nwin = (int)(M - ws);
+  {
+    const char* src = E + ws * ROW_BYTES;
+    for (int i = threadIdx.x; i < nwin * LPR; i += 256) hot[i] = load16<false>(src + (int64_t)i * 16);
+    if constexpr (HAS_W)
+      for (int i = threadIdx.x; i < nwin; i += 256) hotw[i] = w[ws + i];
+  }
+  __syncthreads();
+  // ids are int32: a window that starts past them is never hit
+  const bool reach = ws <= 0x7fffffff;
+  const int32_t ws32 = reach ? (int32_t)ws : 0;
+  const uint32_t nhit = reach ? (uint32_t)nwin : 0u;
+  const uint32_t nm1 = (uint32_t)nwin - 1u;
+
+  const int lane = threadIdx.x & (kWave - 1);
+  const int sub = lane & (LPR - 1);
+  const int g = lane / LPR;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const int64_t stride = nwave * RPI;
+
+  int64_t base = wave * RPI;
+  bool bad = false;
+  {
+    int32_t raw[U][F];
+    if (base < B) load_ids<F, U, false>(raw, idx, base, B, g, RPW, F);
+
+    for (; base < B; base += stride) {
+      int32_t id01[U][2];
+      uint32_t pk[U][PKW];
+      bool miss = false;
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+#pragma unroll
+        for (int j = 0; j < PKW; ++j) pk[u][j] = 0u;
+        bool m = false;
+#pragma unroll
+        for (int f = 0; f < F; ++f) {
+          const int32_t id = clamp_id(raw[u][f], M);
+          bad |= id != raw[u][f];
+          if (f < 2) {
+            id01[u][f] = id;
+          } else {
+            const uint32_t d = (uint32_t)(id - ws32);
+            m |= d >= nhit;
+            pk[u][(f - 2) >> 2] |= (d < nm1 ? d : nm1) << (8 * ((f - 2) & 3));
+          }
+        }
+        miss |= m && (base + (int64_t)u * RPW + g < B);
+      }
+      // wave-uniform: some row of this wave-iteration needs a row outside the
+      // window -> the general loop takes over from this iteration on
+      if (__ballot(miss) != 0) break;
+
+      C c01[U][2];
+      float wg[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+          c01[u][f].template load<NT01>(E + (int64_t)id01[u][f] * ROW_BYTES + sub * 16);
+      }
+      // `w` of the user and item from global memory: lanes sub = 0, 1 own
+      // fields 0, 1 (the other lanes' load is dropped, as in fm_rows_fast)
+      if constexpr (HAS_W) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) wg[u] = w[sub == 1 ? id01[u][1] : id01[u][0]];
+      }
+
+      load_ids<F, U, false>(raw, idx, base + stride, B, g, RPW, F);
+
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        C c[F];
+        c[0] = c01[u][0];
+        c[1] = c01[u][1];
+#pragma unroll
+        for (int f = 2; f < F; ++f) {
+          const uint32_t li = (pk[u][(f - 2) >> 2] >> (8 * ((f - 2) & 3))) & 0xffu;
+          c[f].set(hot[li * LPR + sub]);
+        }
+        float t = group_sum<LPR>(fm_chunk_term<F>(c));
+        float fb = 0.f;
+        if constexpr (HAS_W) {
+          float wv = 0.f;
+#pragma unroll
+          for (int r = 0; r < WPL; ++r) {
+            const int fsel = r * LPR + sub;
+            int j = fsel - 2;
+            j = j < 0 ? 0 : (j > NC - 1 ? NC - 1 : j);
+            uint32_t word = pk[u][0];
+#pragma unroll
+            for (int q = 1; q < PKW; ++q) word = (j >> 2) == q ? pk[u][q] : word;
+            const float wl = hotw[(word >> (8 * (j & 3))) & 0xffu];
+            wv += (fsel < 2) ? wg[u] : ((fsel < F) ? wl : 0.f);
+          }
+          fb = group_sum<LPR>(wv);
+        }
+        const int64_t row = base + (int64_t)u * RPW + g;
+        if (sub == 0 && row < B) out[row] = (t + fb) + w0;
+      }
+    }
+  }
+
+  // general loop: the body of fm_rows_fast at UG row slots, walking the same
+  // wave-iterations UG slots at a time
+  if (base < B) {
+    int u0 = 0;
+    int32_t raw[UG][F];
+    load_ids_slots<F, U, UG>(raw, idx, base, u0, B, g, RPW);
+    while (base < B) {
+      C c[UG][F];
+      int32_t id[UG][F];
+#pragma unroll
+      for (int u = 0; u < UG; ++u)
+#pragma unroll
+        for (int f = 0; f < F; ++f) {
+          id[u][f] = clamp_id(raw[u][f], M);
+          bad |= id[u][f] != raw[u][f];
+          if (NT01 && f < 2)
+            c[u][f].template load<true>(E + (int64_t)id[u][f] * ROW_BYTES + sub * 16);
+          else
+            c[u][f].template load<false>(E + (int64_t)id[u][f] * ROW_BYTES + sub * 16);
+        }
+      float wv[UG];
+      if constexpr (HAS_W) {
+#pragma unroll
+        for (int u = 0; u < UG; ++u) {
+          wv[u] = 0.f;
+#pragma unroll
+          for (int r = 0; r < WPL; ++r) {
+            const int fsel = r * LPR + sub;
+            int32_t my = id[u][0];
+#pragma unroll
+            for (int f = 1; f < F; ++f) my = (fsel == f) ? id[u][f] : my;
+            const float wl = w[my];
+            wv[u] += (fsel < F) ? wl : 0.f;
+          }
+        }
+      }
+      int64_t nbase = base;
+      int nu0 = u0 + UG;
+      if (nu0 >= U) {
+        nu0 = 0;
+        nbase += stride;
+      }
+      load_ids_slots<F, U, UG>(raw, idx, nbase, nu0, B, g, RPW);
+#pragma unroll
+      for (int u = 0; u < UG; ++u) {
+        float t = group_sum<LPR>(fm_chunk_term<F>(c[u]));
+        float fb = 0.f;
+        if constexpr (HAS_W) fb = group_sum<LPR>(wv[u]);
+        const int64_t row = base + (int64_t)(u0 + u) * RPW + g;
+        if (sub == 0 && u0 + u < U && row < B) out[row] = (t + fb) + w0;
+      }
+      base = nbase;
+      u0 = nu0;
+    }
+  }
+  report_bad_id(status, bad);
+}
+
 // Generic fallback (any k, any F <= 64): one wave per row, lanes stride over k.
 template <bool BF16>
 __global__ __launch_bounds__(256) void fm_rows_generic(
@@ -318,12 +576,42 @@ __global__ __launch_bounds__(256) void hybrid_rows_generic(
 // ---------------------------------------------------------------------------
 // dispatch
 // ---------------------------------------------------------------------------
-static int grid_for(int64_t rows, int64_t rows_per_block) {
+static int grid_for(int64_t rows, int64_t rows_per_block, hipStream_t s) {
   int64_t g = (rows + rows_per_block - 1) / rows_per_block;
-  const int64_t cap = 256 * HHFM_K1_CAP;  // 256 CUs x HHFM_K1_CAP blocks; grid-stride the rest
+  // CUs x HHFM_K1_CAP blocks; grid-stride the rest
+  const int64_t cap = (int64_t)stream_cu_count(s) * HHFM_K1_CAP;
   if (g > cap) g = cap;
   if (g < 1) g = 1;
   return (int)g;
+}
+
+// fm_rows_fast_hot: launched when `forced` (HHFM_FLAG_HOT_TAIL) or when its
+// own grid is at the cap, so that every wave loops and the 16 KiB staging per
+// workgroup is amortised; returns false (nothing launched) otherwise.  A
+// forced launch below that size takes a quarter of the uncapped blocks, so
+// its waves iterate too.
+template <int F, int LPR, bool BF16>
+static bool launch_fm_hot(const int32_t* idx, int64_t B, const char* E,
+                          int64_t M, const float* w, float w0, float* out,
+                          bool forced, int32_t* status, hipStream_t s) {
+  constexpr int RPB = 4 * (kWave / LPR) * HotRows<F>::U;
+  const int64_t blocks = (B + RPB - 1) / RPB;
+  const int64_t cap = (int64_t)stream_cu_count(s) * HHFM_K1_HOT_CAP;
+  if (blocks < cap && !forced) return false;
+  int64_t g = blocks >= cap ? cap : blocks / 4;
+  if (g < 1) g = 1;
+  const int grid = (int)g;
+  const bool big = M * (int64_t)LPR * 16 >= ((int64_t)1 << 30);
+  if (w && big)
+    hipLaunchKernelGGL((fm_rows_fast_hot<F, LPR, BF16, true, true>), dim3(grid),
+                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status);
+  else if (w)
+    hipLaunchKernelGGL((fm_rows_fast_hot<F, LPR, BF16, true, false>), dim3(grid),
+                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status);
+  else
+    hipLaunchKernelGGL((fm_rows_fast_hot<F, LPR, BF16, false, false>), dim3(grid),
+                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status);
+  return true;
 }
 
 template <int F, int LPR, bool BF16>
@@ -331,7 +619,7 @@ static void launch_fm_fast(const int32_t* idx, int64_t B, const char* E,
                            int64_t M, const float* w, float w0, float* out,
                            bool nt, int32_t* status, hipStream_t s) {
   constexpr int RPB = 4 * (kWave / LPR) * RowsPerLane<F>::value;
-  const int grid = grid_for(B, RPB);
+  const int grid = grid_for(B, RPB, s);
   // rows far beyond the caches: the user / item rows streamed (NTM 2)
   const bool big = M * (int64_t)LPR * 16 >= ((int64_t)1 << 30);
   if (w && nt)
@@ -353,7 +641,7 @@ static void launch_hybrid_fast(const int32_t* idx, int64_t B, int nctx,
                                const char* E, int64_t M, float* out,
                                int32_t* status, hipStream_t s) {
   constexpr int RPB = 4 * (kWave / LPR) * RowsPerLane<F>::value;
-  const int grid = grid_for(B, RPB);
+  const int grid = grid_for(B, RPB, s);
   hipLaunchKernelGGL((hybrid_rows_fast<F, LPR, BF16>), dim3(grid), dim3(256), 0,
                      s, idx, B, nctx, E, M, out, status);
 }
@@ -394,6 +682,30 @@ static bool try_fm_fast(const int32_t* idx, int64_t B, int F, const char* E,
   return true;
 }
 
+#define HHFM_F_SWITCH_HOT(BF16, ...)                                            \
+  switch (F) {                                                                 \
+    case 3: HHFM_LPR_SWITCH(return launch_fm_hot, 3, BF16, __VA_ARGS__) break; \
+    case 4: HHFM_LPR_SWITCH(return launch_fm_hot, 4, BF16, __VA_ARGS__) break; \
+    case 5: HHFM_LPR_SWITCH(return launch_fm_hot, 5, BF16, __VA_ARGS__) break; \
+    case 6: HHFM_LPR_SWITCH(return launch_fm_hot, 6, BF16, __VA_ARGS__) break; \
+    case 7: HHFM_LPR_SWITCH(return launch_fm_hot, 7, BF16, __VA_ARGS__) break; \
+    case 8: HHFM_LPR_SWITCH(return launch_fm_hot, 8, BF16, __VA_ARGS__) break; \
+    default: return false;                                                     \
+  }
+
+// true: fm_rows_fast_hot launched; false: no such kernel for this shape, or
+// (not forced) a call too small for it
+static bool try_fm_hot(const int32_t* idx, int64_t B, int F, const char* E,
+                       int64_t M, int lpr, bool bf16, const float* w, float w0,
+                       float* out, bool forced, int32_t* status, hipStream_t s) {
+  if (bf16) {
+    HHFM_F_SWITCH_HOT(true, idx, B, E, M, w, w0, out, forced, status, s)
+  } else {
+    HHFM_F_SWITCH_HOT(false, idx, B, E, M, w, w0, out, forced, status, s)
+  }
+  return false;
+}
+
 static bool try_hybrid_fast(const int32_t* idx, int64_t B, int F, int nctx,
                             const char* E, int64_t M, int lpr, bool bf16,
                             float* out, int32_t* status, hipStream_t s) {
@@ -422,18 +734,30 @@ extern "C" int hhfm_fm_score_rows_ex(const int32_t* idx, int64_t B, int32_t F,
                                      void* stream) {
   if (B < 0 || F < 1 || F > 64 || k < 1 || features_M < 1) return HHFM_EINVAL;
   if (dtype != HHFM_F32 && dtype != HHFM_BF16) return HHFM_EINVAL;
-  if (flags & ~HHFM_FLAG_STREAM_TABLE) return HHFM_EINVAL;
+  if (flags & ~(HHFM_FLAG_STREAM_TABLE | HHFM_FLAG_HOT_TAIL | HHFM_FLAG_NO_HOT_TAIL))
+    return HHFM_EINVAL;
+  const bool hot_forced = (flags & HHFM_FLAG_HOT_TAIL) != 0;
+  // the LDS-tail kernel has no all-streaming plan, and cannot be both forced and refused
+  if (hot_forced && (flags & (HHFM_FLAG_NO_HOT_TAIL | HHFM_FLAG_STREAM_TABLE))) return HHFM_EINVAL;
   if (B == 0) return HHFM_OK;
   if (!idx || !E || !out) return HHFM_EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const bool bf16 = dtype == HHFM_BF16;
   const int lpr = lpr_for(k, dtype);
   const bool aligned = (reinterpret_cast<uintptr_t>(E) & 15) == 0;
+  if (HHFM_K1_HOT_AUTO || hot_forced) {
+    const bool allowed = !(flags & (HHFM_FLAG_NO_HOT_TAIL | HHFM_FLAG_STREAM_TABLE));
+    if (allowed && lpr && aligned &&
+        try_fm_hot(idx, B, F, reinterpret_cast<const char*>(E), features_M, lpr, bf16, w, w0,
+                   out, hot_forced, status, s))
+      return (int)hipGetLastError();
+    if (hot_forced) return HHFM_EUNSUPPORTED;   // F outside 3..8, or rows not whole 16-B chunks
+  }
   if (!(lpr && aligned &&
         try_fm_fast(idx, B, F, reinterpret_cast<const char*>(E), features_M,
                     lpr, bf16, w, w0, out, (flags & HHFM_FLAG_STREAM_TABLE) != 0, status,
                     s))) {
-    const int grid = grid_for(B, 4);
+    const int grid = grid_for(B, 4, s);
     if (bf16)
       hipLaunchKernelGGL(fm_rows_generic<true>, dim3(grid), dim3(256), 0, s, idx,
                          B, F, reinterpret_cast<const char*>(E), features_M, k,
@@ -489,7 +813,7 @@ extern "C" int hhfm_hybrid_score_rows_ex(const int32_t* idx, int64_t B,
         try_hybrid_fast(idx, B, ncols, nctx,
                         reinterpret_cast<const char*>(E), features_M, lpr,
                         bf16, out, status, s))) {
-    const int grid = grid_for(B, 4);
+    const int grid = grid_for(B, 4, s);
     if (bf16)
       hipLaunchKernelGGL(hybrid_rows_generic<true>, dim3(grid), dim3(256), 0, s,
                          idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,

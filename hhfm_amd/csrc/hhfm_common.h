@@ -40,27 +40,28 @@ template <>
 struct Chunk<false> {
   static constexpr int kElems = 4;
   float v[4];
-  template <bool NT = false>
-  HHFM_DEV void load(const void* p) {
-    const u32x4_t x = load16<NT>(p);
+  // from the 16 bytes as loaded (any address space)
+  HHFM_DEV void set(const u32x4_t x) {
     v[0] = __uint_as_float(x[0]); v[1] = __uint_as_float(x[1]);
     v[2] = __uint_as_float(x[2]); v[3] = __uint_as_float(x[3]);
   }
+  template <bool NT = false>
+  HHFM_DEV void load(const void* p) { set(load16<NT>(p)); }
 };
 
 template <>
 struct Chunk<true> {
   static constexpr int kElems = 8;
   float v[8];
-  template <bool NT = false>
-  HHFM_DEV void load(const void* p) {
-    const u32x4_t x = load16<NT>(p);
+  HHFM_DEV void set(const u32x4_t x) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       v[2 * i] = __uint_as_float(x[i] << 16);             // low bf16
       v[2 * i + 1] = __uint_as_float(x[i] & 0xffff0000u);  // high bf16
     }
   }
+  template <bool NT = false>
+  HHFM_DEV void load(const void* p) { set(load16<NT>(p)); }
 };
 
 HHFM_DEV float bf16_to_f32(uint16_t b) { return __uint_as_float(uint32_t(b) << 16); }

@@ -38,6 +38,9 @@ PYBIND11_MODULE(_hhfm, m) {
   m.attr("BF16") = (int)HHFM_BF16;
   m.attr("MODE_FM") = (int)HHFM_MODE_FM;
   m.attr("MODE_HHFM") = (int)HHFM_MODE_HHFM;
+  m.attr("FLAG_STREAM_TABLE") = HHFM_FLAG_STREAM_TABLE;
+  m.attr("FLAG_HOT_TAIL") = HHFM_FLAG_HOT_TAIL;
+  m.attr("FLAG_NO_HOT_TAIL") = HHFM_FLAG_NO_HOT_TAIL;
   m.attr("PLAN_EXACT_FP32") = HHFM_PLAN_EXACT_FP32;
   m.attr("PLAN_NO_SEED") = HHFM_PLAN_NO_SEED;
   m.attr("PLAN_NO_RING") = HHFM_PLAN_NO_RING;

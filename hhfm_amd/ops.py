@@ -116,7 +116,9 @@ def fm_score_rows(idx: torch.Tensor, E: torch.Tensor, w: Optional[torch.Tensor],
                   w0: float = 0.0, out: Optional[torch.Tensor] = None,
                   status: Optional[torch.Tensor] = None, flags: int = 0) -> torch.Tensor:
     """FM.out (FM.py:99-120) for rows ``idx`` [B, F] -> float32 [B].
-    ``status``: optional device int32 word the kernel flags bad ids in."""
+    ``status``: optional device int32 word the kernel flags bad ids in.
+    ``flags``: HHFM_FLAG_* bits of include/hhfm.h, passed through (1 streams
+    the table, 2 / 4 force / refuse the LDS-tail kernel; same bits out)."""
     _idx(idx, "idx")
     dev = _need_cuda(idx, E, w, out)
     B, F = idx.shape

@@ -108,6 +108,19 @@ int hhfm_fm_score_rows(const int32_t* idx, int64_t B, int32_t F,
 /* Same, with tuning flags and an optional id status word:
  *   HHFM_FLAG_STREAM_TABLE — read embedding rows / ids and write `out` with
  *   non-temporal accesses (measured 10 % slower at configs[1]).
+ *   HHFM_FLAG_HOT_TAIL / HHFM_FLAG_NO_HOT_TAIL — force / refuse the LDS-tail
+ *   kernel: for 3 <= F <= 8 and rows of whole 16-byte chunks
+ *   every workgroup stages the table's last 16 KiB of rows (and their `w`) in
+ *   LDS and reads columns 2.. from there, which is where the loaders' column-
+ *   major token numbering puts the small context vocabularies; rows with an
+ *   id of columns 2.. outside that window are computed from global memory by
+ *   the same kernel.  The same bits as the default kernel for any input.
+ *   Automatic rule (neither bit): taken when the call is large enough that
+ *   its grid is at the per-CU block cap (about 1.6 M rows at k = 64 fp32), so
+ *   the staging is amortised, and HHFM_FLAG_STREAM_TABLE is not set.
+ *   HOT_TAIL forces it at any B (HHFM_EUNSUPPORTED when the shape has no such
+ *   kernel); NO_HOT_TAIL keeps the default kernel.  HOT_TAIL together with
+ *   NO_HOT_TAIL or STREAM_TABLE is HHFM_EINVAL.
  *   Any other bit is rejected with HHFM_EINVAL.
  *   Without the flag, a table of 1 GiB or more (far beyond the caches) loads
  *   the first two columns' rows — the user and item, read once per launch —
@@ -118,6 +131,8 @@ int hhfm_fm_score_rows(const int32_t* idx, int64_t B, int32_t F,
  *   kernel cannot fault).  hhfm_status_read() turns it into HHFM_EINVAL —
  *   the InvalidArgumentError tf.nn.embedding_lookup raises (FM.py:99). */
 #define HHFM_FLAG_STREAM_TABLE 1
+#define HHFM_FLAG_HOT_TAIL 2
+#define HHFM_FLAG_NO_HOT_TAIL 4
 #define HHFM_FM_ROWS_DEFAULT_FLAGS 0
 #define HHFM_STATUS_BAD_ID 1
 int hhfm_fm_score_rows_ex(const int32_t* idx, int64_t B, int32_t F,

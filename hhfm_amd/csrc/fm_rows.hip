@@ -12,8 +12,10 @@
 //     the index rows of the NEXT iteration are fetched before this
 //     iteration's gathers are consumed (hides the idx->gather dependency);
 //   * the ½((Σv)²−Σv²) interaction is reduced first inside the lane (4 or 8
-//     elements), then across the LPR lanes with a DPP/ds_swizzle butterfly —
-//     no LDS allocation, no atomics, one fp32 store per row.
+//     elements), then across the LPR lanes by group_sum_dpp (hhfm_common.h):
+//     the xor-8/4/2/1 steps are v_add_f32_dpp (row_ror / quad_perm) and only
+//     the xor-32/16 steps of LPR 64 / 32 go through ds_bpermute_b32 (LDS
+//     hardware, no LDS allocation).  No atomics, one fp32 store per row.
 #include "hhfm_common.h"
 
 namespace hhfm {
@@ -86,6 +88,7 @@ __global__ __launch_bounds__(256) void fm_rows_fast(
   constexpr int64_t ROW_BYTES = (int64_t)LPR * 16;
   constexpr bool NT = NTM == 1;
   using C = Chunk<BF16>;
+  const uint32_t M32 = id_limit32(M);
 
   const int lane = threadIdx.x & (kWave - 1);
   const int sub = lane & (LPR - 1);
@@ -106,7 +109,7 @@ __global__ __launch_bounds__(256) void fm_rows_fast(
     for (int u = 0; u < U; ++u)
 #pragma unroll
       for (int f = 0; f < F; ++f) {
-        id[u][f] = clamp_id(raw[u][f], M);
+        id[u][f] = clamp_id32(raw[u][f], M32);
         bad |= id[u][f] != raw[u][f];
         if (HHFM_K1_CTXKO && f >= 2) {
 #pragma unroll
@@ -157,9 +160,9 @@ __global__ __launch_bounds__(256) void fm_rows_fast(
         }
         t += 0.5f * (s * s - q);
       }
-      t = group_sum<LPR>(t);
+      t = group_sum_dpp<LPR>(t);
       float fb = 0.f;
-      if constexpr (HAS_W) fb = group_sum<LPR>(wv[u]);
+      if constexpr (HAS_W) fb = group_sum_dpp<LPR>(wv[u]);
       const int64_t row = base + (int64_t)u * RPW + g;
       if (sub == 0 && row < B) {
         if constexpr (NT) __builtin_nontemporal_store((t + fb) + w0, out + row);
@@ -260,6 +263,7 @@ __global__ __launch_bounds__(256) void fm_rows_fast_hot(
   constexpr int WPL = (F + LPR - 1) / LPR;
   static_assert(T <= 256, "local index is 8 bits");
   using C = Chunk<BF16>;
+  const uint32_t M32 = id_limit32(M);
 
   __shared__ u32x4_t hot[T * LPR];
   __shared__ float hotw[HAS_W ? T : 1];
@@ -304,7 +308,7 @@ __global__ __launch_bounds__(256) void fm_rows_fast_hot(
         bool m = false;
 #pragma unroll
         for (int f = 0; f < F; ++f) {
-          const int32_t id = clamp_id(raw[u][f], M);
+          const int32_t id = clamp_id32(raw[u][f], M32);
           bad |= id != raw[u][f];
           if (f < 2) {
             id01[u][f] = id;
@@ -347,7 +351,10 @@ __global__ __launch_bounds__(256) void fm_rows_fast_hot(
           const uint32_t li = (pk[u][(f - 2) >> 2] >> (8 * ((f - 2) & 3))) & 0xffu;
           c[f].set(hot[li * LPR + sub]);
         }
-        float t = group_sum<LPR>(fm_chunk_term<F>(c));
+        // the row sum is reduced before the `w` terms are formed: stepping
+        // the two sums together fills the DPP hazard slots but ran 0.45 %
+        // slower and takes F = 6 bf16 past 168 VGPRs (profiles/k1_consume_ab.txt)
+        float t = group_sum_dpp<LPR>(fm_chunk_term<F>(c));
         float fb = 0.f;
         if constexpr (HAS_W) {
           float wv = 0.f;
@@ -362,7 +369,7 @@ __global__ __launch_bounds__(256) void fm_rows_fast_hot(
             const float wl = hotw[(word >> (8 * (j & 3))) & 0xffu];
             wv += (fsel < 2) ? wg[u] : ((fsel < F) ? wl : 0.f);
           }
-          fb = group_sum<LPR>(wv);
+          fb = group_sum_dpp<LPR>(wv);
         }
         const int64_t row = base + (int64_t)u * RPW + g;
         if (sub == 0 && row < B) out[row] = (t + fb) + w0;
@@ -383,7 +390,7 @@ __global__ __launch_bounds__(256) void fm_rows_fast_hot(
       for (int u = 0; u < UG; ++u)
 #pragma unroll
         for (int f = 0; f < F; ++f) {
-          id[u][f] = clamp_id(raw[u][f], M);
+          id[u][f] = clamp_id32(raw[u][f], M32);
           bad |= id[u][f] != raw[u][f];
           if (NT01 && f < 2)
             c[u][f].template load<true>(E + (int64_t)id[u][f] * ROW_BYTES + sub * 16);
@@ -415,9 +422,9 @@ __global__ __launch_bounds__(256) void fm_rows_fast_hot(
       load_ids_slots<F, U, UG>(raw, idx, nbase, nu0, B, g, RPW);
 #pragma unroll
       for (int u = 0; u < UG; ++u) {
-        float t = group_sum<LPR>(fm_chunk_term<F>(c[u]));
+        float t = group_sum_dpp<LPR>(fm_chunk_term<F>(c[u]));
         float fb = 0.f;
-        if constexpr (HAS_W) fb = group_sum<LPR>(wv[u]);
+        if constexpr (HAS_W) fb = group_sum_dpp<LPR>(wv[u]);
         const int64_t row = base + (int64_t)(u0 + u) * RPW + g;
         if (sub == 0 && u0 + u < U && row < B) out[row] = (t + fb) + w0;
       }
@@ -477,6 +484,7 @@ __global__ __launch_bounds__(256) void hybrid_rows_fast(
   constexpr int RPI = RPW * U;
   constexpr int64_t ROW_BYTES = (int64_t)LPR * 16;
   using C = Chunk<BF16>;
+  const uint32_t M32 = id_limit32(M);
 
   const int lane = threadIdx.x & (kWave - 1);
   const int sub = lane & (LPR - 1);
@@ -498,7 +506,7 @@ __global__ __launch_bounds__(256) void hybrid_rows_fast(
     for (int u = 0; u < U; ++u)
 #pragma unroll
       for (int f = 0; f < F; ++f) {
-        id[u][f] = clamp_id(raw[u][f], M);
+        id[u][f] = clamp_id32(raw[u][f], M32);
         bad |= id[u][f] != raw[u][f];
         c[u][f].load(E + (int64_t)id[u][f] * ROW_BYTES + sub * 16);
       }
@@ -522,7 +530,7 @@ __global__ __launch_bounds__(256) void hybrid_rows_fast(
         if (ctx_end < F) h = h + tim;
         t += h * c[u][1].v[e];
       }
-      t = group_sum<LPR>(t);
+      t = group_sum_dpp<LPR>(t);
       const int64_t row = base + (int64_t)u * RPW + g;
       if (sub == 0 && row < B) out[row] = t;
     }

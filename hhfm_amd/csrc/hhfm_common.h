@@ -96,6 +96,66 @@ HHFM_DEV float group_sum(float x) {
   return x;
 }
 
+// In-register form of group_sum for the row kernels: the same partner (lane
+// xor m) and the same order of steps m = G/2 .. 1, so the same bits, with the
+// steps m <= 8 done by DPP inside a row of 16 lanes instead of a round trip
+// through LDS (__shfl_xor is ds_bpermute_b32 + lgkmcnt wait).  Every lane of
+// the wave must be active.
+//   m = 8        row_ror:8
+//   m = 4, G>=16 row_ror:4 — lane i reads lane (i - 4) mod 16, which is lane
+//                i ^ 4 or i ^ 4 ^ 8; after the m = 8 step the two hold the
+//                same value
+//   m = 4, G = 8 row_shl:4 into banks 0, 2 and row_shr:4 into banks 1, 3
+//   m = 2, 1     quad_perm [2,3,0,1], [1,0,3,2]
+// The compiler folds each move into v_add_f32_dpp.
+constexpr int kDppQuadXor1 = 0xB1;  // quad_perm [1,0,3,2]
+constexpr int kDppQuadXor2 = 0x4E;  // quad_perm [2,3,0,1]
+constexpr int kDppRowShl4 = 0x104;
+constexpr int kDppRowShr4 = 0x114;
+constexpr int kDppRowRor4 = 0x124;
+constexpr int kDppRowRor8 = 0x128;
+
+template <int CTRL>
+HHFM_DEV float dpp_read(float x) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
+}
+
+// the value of lane xor M (M <= 8 within a row of 16 lanes, else by LDS);
+// PERIODIC8: x is known to be equal in lanes i and i ^ 8
+template <int M, bool PERIODIC8>
+HHFM_DEV float xor_partner(float x) {
+  if constexpr (M == 1) return dpp_read<kDppQuadXor1>(x);
+  else if constexpr (M == 2) return dpp_read<kDppQuadXor2>(x);
+  else if constexpr (M == 4 && PERIODIC8) return dpp_read<kDppRowRor4>(x);
+  else if constexpr (M == 4) {
+    const int xi = __float_as_int(x);
+    int r = __builtin_amdgcn_update_dpp(xi, xi, kDppRowShl4, 0xf, 0x5, false);
+    r = __builtin_amdgcn_update_dpp(r, xi, kDppRowShr4, 0xf, 0xa, false);
+    return __int_as_float(r);
+  } else if constexpr (M == 8) return dpp_read<kDppRowRor8>(x);
+  else return __shfl_xor(x, M, kWave);
+}
+
+template <int G>
+HHFM_DEV float group_sum_dpp(float x) {
+  static_assert(G >= 1 && G <= kWave && (G & (G - 1)) == 0, "aligned power-of-two groups");
+  if constexpr (G >= 64) x += xor_partner<32, false>(x);
+  if constexpr (G >= 32) x += xor_partner<16, false>(x);
+  if constexpr (G >= 16) x += xor_partner<8, false>(x);
+  if constexpr (G >= 8) x += xor_partner<4, (G >= 16)>(x);
+  if constexpr (G >= 4) x += xor_partner<2, false>(x);
+  if constexpr (G >= 2) x += xor_partner<1, false>(x);
+  return x;
+}
+
+// 32-bit form of clamp_id for kernels that clamp many ids per iteration:
+// M32 = id_limit32(M) once per kernel; an int32 id is in [0, M) iff
+// (uint32_t)id < M32 (a negative id is >= 2^31 as unsigned).
+HHFM_DEV uint32_t id_limit32(int64_t M) {
+  return M < ((int64_t)1 << 31) ? (uint32_t)M : 0x80000000u;
+}
+HHFM_DEV int32_t clamp_id32(int32_t id, uint32_t M32) { return (uint32_t)id < M32 ? id : 0; }
+
 // CUs of the device that owns `st` (the stream's device, not the calling
 // thread's current one), cached per device: the persistent grids ask per call
 inline int stream_cu_count(hipStream_t st) {

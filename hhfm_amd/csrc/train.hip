@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void fm_train_rows(
         atomicAdd(dE + id * k + c, g * (s - E[id * k + c]));   // ∂out/∂e_f = Σe − e_f
       }
     }
-    if (l < F) atomicAdd(dw + clamp_id(x[l], M), g);
+    for (int f = l; f < F; f += kWave) atomicAdd(dw + clamp_id(x[f], M), g);
     if (l == 0) {
       atomicAdd(scal + 0, g);
       atomicAdd(scal + 1, 0.5f * r * r);
@@ -494,11 +494,15 @@ static bool dfm_train_plan(int64_t B, int F, int k, int64_t M, int L, const int3
   int64_t o = 0;
   auto take = [&](int64_t n) { const int64_t r = o; o += (n + 63) & ~int64_t(63); return r; };
   // zero-initialised, kept zeroed by the step (scalars incl. Adam's β powers,
-  // dE, dw, touched mask): first, at B-independent offsets, so a workspace
+  // dE, dw, dWp, touched mask): first, at B-independent offsets, so a workspace
   // grown for a larger batch keeps its state by copying the old one's bytes
+  // and a smaller batch finds every buffer the step accumulates into where the
+  // last step left it zeroed (what follows the prefix is per-batch scratch
+  // that a step writes before it reads it, so it may move with B)
   p.off_scal = take(16);
   p.off_dE = take(M * k);
   p.off_dw = take(M);
+  p.off_dWp = take(F + k + p.d[L]);
   p.off_touch = take((M + 3) / 4);   // touched-row mask, M bytes
   for (int i = 0; i < L; ++i) {
     p.off_WtP[i] = take((int64_t)p.d[i + 1] * pad8(p.d[i]));
@@ -514,7 +518,6 @@ static bool dfm_train_plan(int64_t B, int F, int k, int64_t M, int L, const int3
   }
   p.off_dX0 = take(p.Bp * p.D0);
   p.off_g = take(p.Bp);
-  p.off_dWp = take(F + k + p.d[L]);
   p.total = o;
   return true;
 }
@@ -802,7 +805,8 @@ extern "C" int hhfm_fm_train_step(const int32_t* idx, const float* y, int64_t B,
                                   float* loss, void* stream) {
   if (B < 0 || F < 1 || k < 1 || features_M < 1) return HHFM_EINVAL;
   if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
-  if (!idx || !y || !E || !w || !w0 || !loss || !workspace) return HHFM_EINVAL;
+  if (!E || !w || !w0 || !loss || !workspace) return HHFM_EINVAL;
+  if (B > 0 && (!idx || !y)) return HHFM_EINVAL;   // an empty batch reads no rows
   if (optimizer != OPT_SGD && (!accE || !accw || !accw0)) return HHFM_EINVAL;
   if (ws_bytes < hhfm_train_workspace(features_M, k)) return HHFM_EWORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -840,7 +844,8 @@ extern "C" int hhfm_hhfm_train_step(const int32_t* X, const int32_t* Neg, int64_
   if (B < 0 || ncols < 2 || NG < 1 || k < 1 || features_M < 1) return HHFM_EINVAL;
   if (NG > kMaxNeg) return HHFM_EUNSUPPORTED;
   if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
-  if (!X || !Neg || !E || !loss || !workspace) return HHFM_EINVAL;
+  if (!E || !loss || !workspace) return HHFM_EINVAL;
+  if (B > 0 && (!X || !Neg)) return HHFM_EINVAL;
   if (optimizer != OPT_SGD && !accE) return HHFM_EINVAL;
   if (ws_bytes < hhfm_train_workspace(features_M, k)) return HHFM_EWORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -885,7 +890,7 @@ extern "C" int hhfm_dfm_train_workspace(int64_t B, int32_t F, int32_t k, int64_t
 }
 
 // bytes at the front of the DeepFM workspace that carry state between steps
-// (scalars incl. Adam's β powers, dE, dw, the touched mask); B-independent
+// (scalars incl. Adam's β powers, dE, dw, dWp, the touched mask); B-independent
 extern "C" int hhfm_dfm_train_state_bytes(int32_t F, int32_t k, int64_t features_M,
                                           int32_t nlayers, const int32_t* layer_dims,
                                           size_t* state_bytes) {
@@ -909,8 +914,8 @@ extern "C" int hhfm_dfm_train_step(const int32_t* idx, const float* y, int64_t B
       !dfm_train_plan(B, F, k, features_M, nlayers, layer_dims, p))
     return HHFM_EINVAL;
   if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
-  if (!idx || !y || !E || !w || !W || !bias || !Wp || !bp || !loss || !workspace)
-    return HHFM_EINVAL;
+  if (!E || !w || !W || !bias || !Wp || !bp || !loss || !workspace) return HHFM_EINVAL;
+  if (B > 0 && (!idx || !y)) return HHFM_EINVAL;
   const int L = p.L;
   for (int i = 0; i < L; ++i)
     if (!W[i] || !bias[i]) return HHFM_EINVAL;
@@ -1081,8 +1086,8 @@ extern "C" int hhfm_afm_train_step(const int32_t* idx, const float* y, int64_t B
   AfmTrainPlan p;
   if (!afm_train_plan(B, F, k, A, features_M, p)) return HHFM_EINVAL;
   if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
-  if (!idx || !y || !E || !w || !w0 || !W || !b || !pvec || !P || !loss || !workspace)
-    return HHFM_EINVAL;
+  if (!E || !w || !w0 || !W || !b || !pvec || !P || !loss || !workspace) return HHFM_EINVAL;
+  if (B > 0 && (!idx || !y)) return HHFM_EINVAL;
   if (optimizer != OPT_SGD) {   // acc: E, w, w0, W, b, pvec, P
     if (!acc) return HHFM_EINVAL;
     for (int i = 0; i < 7; ++i)

@@ -403,6 +403,9 @@ int hhfm_afm_catalog_topk_ex(const int32_t* qidx, int64_t B, int32_t F, const vo
  * must be zero-filled once; the step leaves it zeroed except Adam's β powers.  HHFM: X [B][ncols]
  * full rows [user, item, ctx..., time...], Neg [B][NG] negative item ids,
  * NG <= 16.
+ * B = 0 is a step like any other in all four train entry points (the l2
+ * term still decays its variable, Adam's moments and powers still advance);
+ * the row pointers (idx / X, y / Neg) may then be NULL.
  * ---------------------------------------------------------------------- */
 size_t hhfm_train_workspace(int64_t features_M, int32_t k);
 int hhfm_fm_train_step(const int32_t* idx, const float* y, int64_t B, int32_t F, float* E,
@@ -425,8 +428,9 @@ int hhfm_hhfm_train_step(const int32_t* X, const int32_t* Neg, int64_t B, int32_
  * b_0..b_{L-1}, Wp, bp, sized and initialised as above.
  * The workspace (hhfm_dfm_train_workspace bytes for batches of at most B rows)
  * must be zero-filled once; the step keeps its gradient regions zeroed.  Its
- * persistent part (gradients, Adam's β powers) leads at offsets independent
- * of B: a workspace grown for a larger batch keeps the state when that
+ * persistent part (every gradient the step accumulates into, Adam's β
+ * powers) leads at offsets independent of B, so a later smaller batch finds
+ * it where the last step left it, and a workspace grown for a larger batch keeps the state when that
  * prefix (hhfm_dfm_train_state_bytes) is copied into the new zero-filled one.
  * Requires k % 4 == 0, L <= 4, F + k + d_{L-1} <= 1024. */
 int hhfm_dfm_train_workspace(int64_t B, int32_t F, int32_t k, int64_t features_M,

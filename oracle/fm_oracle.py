@@ -498,7 +498,7 @@ def afm_train_step(X, y, E, w, w0, W, b, pvec, P, acc, lr, lam, optimizer="adagr
     k, A = W.shape
     e = E[X]                                                          # :104
     pr = _pairs(e)                                                    # :107-112 [B,np,k]
-    z = (np.matmul(pr.reshape(-1, k), W).astype(F32) + b).reshape(B, -1, A)   # :117
+    z = (np.matmul(pr.reshape(-1, k), W).astype(F32) + b).reshape(B, pr.shape[1], A)   # :117
     r = np.maximum(z, 0)
     logit = (pvec * r).sum(-1, dtype=F32)                             # :121-124 [B,np]
     ex = np.exp(logit - logit.max(1, keepdims=True))

@@ -20,20 +20,34 @@
 // accumulates Σ var² of the pre-update table for the reported loss (TF
 // evaluates `loss` and the update in the same run).
 // Gradients of reduce_max split equally between tied maxima (TF _MaxGrad).
+//
+// Workspaces.  Every step keeps a block of kScalFloats scalars (`scal`, slots
+// below), dense gradient buffers that the optimizer leaves zeroed, and a byte
+// mask of the rows a batch touched.  The byte layouts are stated once each, in
+// the plan functions: fm_train_plan (FM and HHFM), dfm_train_plan and
+// afm_train_plan (their shared persistent prefix in TrainWs).  The optimizer
+// tail every step ends with is optimizer_tail.
 #include <cfloat>
+#include <initializer_list>
+#include <iterator>
 
 #include "gemm_mfma.h"
 
 namespace hhfm {
 
-enum { OPT_ADAGRAD = 0, OPT_SGD = 1 };
 constexpr int kMaxNeg = 16;   // negatives per row (the reference samples 10, OurModel7.py:371)
 
-// scal[0] = Σ dL/d(w0)  scal[1] = data loss  scal[2] = Σ E² (pre-update)  scal[3] = Σ w² (unused)
-// scal[8], scal[9] = Adam's β1^t, β2^t (kept between steps); scal[10] != 0 once
-// Adam has taken a step (a separate flag: β1^t underflows to exactly 0 after
-// 828 steps (TF's flush-to-zero), and TF then keeps using 0, so 0 cannot also
-// mean "not started")
+// The scalar block's slots.  kScalAdam: Adam's β1^t, β2^t (kept between steps)
+// and a flag that is != 0 once Adam has taken a step (a separate flag: β1^t
+// underflows to exactly 0 after 828 steps (TF's flush-to-zero), and TF then
+// keeps using 0, so 0 cannot also mean "not started").  finish_loss zeroes
+// floats 0..3 (3 is unused).
+constexpr int kScalBiasGrad = 0;   // Σ dL/d(out): the gradient of w0 / bp
+constexpr int kScalDataLoss = 1;   // the batch's loss without the l2 term
+constexpr int kScalSumSq = 2;      // Σ var² (pre-update) of the l2-regularised variables
+constexpr int kScalAdam = 8;       // [β1^t, β2^t, started]
+constexpr int kScalFloats = 16;
+
 __global__ __launch_bounds__(256) void fm_train_rows(
     const int32_t* __restrict__ idx, const float* __restrict__ y, int64_t B, int F,
     const float* __restrict__ E, const float* __restrict__ w, const float* __restrict__ w0,
@@ -69,8 +83,8 @@ __global__ __launch_bounds__(256) void fm_train_rows(
     }
     for (int f = l; f < F; f += kWave) atomicAdd(dw + clamp_id(x[f], M), g);
     if (l == 0) {
-      atomicAdd(scal + 0, g);
-      atomicAdd(scal + 1, 0.5f * r * r);
+      atomicAdd(scal + kScalBiasGrad, g);
+      atomicAdd(scal + kScalDataLoss, 0.5f * r * r);
     }
   }
 }
@@ -143,7 +157,7 @@ __global__ __launch_bounds__(256) void hhfm_train_rows(
       for (int j = c0; j < c1; ++j) atomicAdd(dE + (int64_t)clamp_id(x[j], M) * k + c, dh);
       for (int j = t0; j < t1; ++j) atomicAdd(dE + (int64_t)clamp_id(x[j], M) * k + c, dh);
     }
-    if (l == 0) atomicAdd(scal + 1, -logf(sg));
+    if (l == 0) atomicAdd(scal + kScalDataLoss, -logf(sg));
   }
 }
 
@@ -163,7 +177,6 @@ __global__ __launch_bounds__(256) void hhfm_train_rows(
 // state: Adagrad / Momentum n floats, Adam 2n (m, then v).  pw: the step's
 // β1^t, β2^t (TF's beta1_power / beta2_power) and the started flag pw[2]
 // (0 = the first step, whose powers are β1, β2).
-enum { OPT_MOMENTUM = 2, OPT_ADAM = 3 };
 constexpr float kMomentum = 0.95f, kBeta1 = 0.9f, kBeta2 = 0.999f, kAdamEps = 1e-8f;
 
 struct OptStep {
@@ -181,7 +194,7 @@ __global__ __launch_bounds__(256) void optimizer_apply(float* __restrict__ var,
                                                        float lam, OptStep o,
                                                        float* __restrict__ sumsq) {
   float alpha = 0.f;
-  if (o.opt == OPT_ADAM) {
+  if (o.opt == HHFM_OPT_ADAM) {
     const bool started = o.pw[2] != 0.f;
     const float b1p = started ? o.pw[0] : kBeta1;
     const float b2p = started ? o.pw[1] : kBeta2;
@@ -193,13 +206,13 @@ __global__ __launch_bounds__(256) void optimizer_apply(float* __restrict__ var,
     const float v = var[i];
     ss += v * v;
     const float g = grad[i] + lam * v;
-    if (o.opt == OPT_ADAGRAD) {
+    if (o.opt == HHFM_OPT_ADAGRAD) {
       const float a = state[i] + g * g;
       state[i] = a;
       var[i] = v - o.lr * g * rsqrtf(a);
-    } else if (o.opt == OPT_SGD) {
+    } else if (o.opt == HHFM_OPT_SGD) {
       var[i] = v - o.lr * g;
-    } else if (o.opt == OPT_MOMENTUM) {
+    } else if (o.opt == HHFM_OPT_MOMENTUM) {
       if (!o.sparse || o.touched[i / o.rowlen]) {
         const float a = state[i] * kMomentum + g;
         state[i] = a;
@@ -250,7 +263,7 @@ __global__ __launch_bounds__(256) void mark_rows(const int32_t* __restrict__ idx
 }
 
 __global__ void finish_loss(float* scal, float lam, float* loss) {
-  loss[0] = scal[1] + lam * 0.5f * scal[2];   // + l2_regularizer(λ)(E) = λ·ΣE²/2
+  loss[0] = scal[kScalDataLoss] + lam * 0.5f * scal[kScalSumSq];   // + l2_regularizer(λ)(var)
   scal[0] = scal[1] = scal[2] = scal[3] = 0.f;
 }
 
@@ -260,17 +273,85 @@ static int grid_for_n(int64_t n) {
 }
 
 static bool opt_ok(int opt) {
-  return opt == OPT_ADAGRAD || opt == OPT_SGD || opt == OPT_MOMENTUM || opt == OPT_ADAM;
+  return opt == HHFM_OPT_ADAGRAD || opt == HHFM_OPT_SGD || opt == HHFM_OPT_MOMENTUM ||
+         opt == HHFM_OPT_ADAM;
 }
 
-// one optimizer_apply launch; `sparse` variables under Momentum need the
-// touched mask (`mark_rows` before, cleared after by the caller)
-static void apply_opt(float* var, float* grad, float* state, int64_t n, float lam, int opt,
-                      float lr, const float* pw, const uint8_t* touched, int rowlen, bool sparse,
-                      float* sumsq, hipStream_t st) {
-  OptStep o{opt, lr, pw, touched, rowlen > 0 ? rowlen : 1, sparse ? 1 : 0};
-  hipLaunchKernelGGL(optimizer_apply, dim3(grid_for_n(n)), dim3(256), 0, st, var, grad, state, n,
-                     lam, o, sumsq);
+// the optimizer's slot arrays: `acc` holds n non-null entries, unless SGD (which keeps none)
+static bool slots_ok(int opt, float* const* acc, int n) {
+  if (opt == HHFM_OPT_SGD) return true;
+  if (!acc) return false;
+  for (int i = 0; i < n; ++i)
+    if (!acc[i]) return false;
+  return true;
+}
+
+static float* slot_of(int opt, float* const* acc, int i) {
+  return opt != HHFM_OPT_SGD ? acc[i] : nullptr;
+}
+
+// One variable of a step, as the optimizer tail sees it.
+struct OptVar {
+  float* var;
+  float* grad;    // dense gradient buffer, n floats; left zeroed
+  float* slot;    // the optimizer's slot array (null under SGD)
+  int64_t n;
+  float lam;      // g = grad + lam·var
+  int rowlen;     // elements per table row (the touched mask's index is i / rowlen)
+  bool sparse;    // the variable's TF gradient is an IndexedSlices
+  bool sumsq;     // Σ var² (pre-update) goes into the loss's l2 term
+};
+
+struct IdList {
+  const int32_t* ids;
+  int64_t n;
+};
+
+// What every step ends with: under Momentum the rows of `ids` are marked in
+// `touched` for the sparse variables (and unmarked afterwards: the mask is
+// left zeroed), one optimizer_apply per variable in list order, Adam's powers
+// advance, and finish_loss writes loss = data loss + loss_lam·Σvar²/2 and
+// clears the scalars.  Returns hipGetLastError().
+static int optimizer_tail(const OptVar* vars, int nvars, std::initializer_list<IdList> ids,
+                          int64_t M, int opt, float lr, float* scal, uint8_t* touched,
+                          float loss_lam, float* loss, hipStream_t st) {
+  bool mark = false;
+  for (int i = 0; i < nvars; ++i) mark |= opt == HHFM_OPT_MOMENTUM && vars[i].sparse;
+  auto set_mask = [&](uint8_t val) {
+    for (const IdList& l : ids)
+      if (mark && l.n > 0)   // an empty batch touches no row
+        hipLaunchKernelGGL(mark_rows, dim3(grid_for_n(l.n)), dim3(256), 0, st, l.ids, l.n, M,
+                           touched, val);
+  };
+  set_mask(1);
+  for (int i = 0; i < nvars; ++i) {
+    const OptVar& v = vars[i];
+    OptStep o{opt, lr, scal + kScalAdam, v.sparse ? touched : nullptr, v.rowlen, v.sparse ? 1 : 0};
+    hipLaunchKernelGGL(optimizer_apply, dim3(grid_for_n(v.n)), dim3(256), 0, st, v.var, v.grad,
+                       v.slot, v.n, v.lam, o, v.sumsq ? scal + kScalSumSq : nullptr);
+  }
+  set_mask(0);
+  if (opt == HHFM_OPT_ADAM)
+    hipLaunchKernelGGL(adam_advance, dim3(1), dim3(1), 0, st, scal + kScalAdam);
+  hipLaunchKernelGGL(finish_loss, dim3(1), dim3(1), 0, st, scal, loss_lam, loss);
+  return (int)hipGetLastError();
+}
+
+// The FM / HHFM workspace: dE [M·k] | dw [M] | scal [kScalFloats] floats, then
+// the touched mask, M bytes rounded up to 256.  Zero-filled once by the caller.
+struct FmTrainPlan {
+  int64_t off_dE, off_dw, off_scal, off_touch;   // floats
+  size_t bytes;
+};
+
+static FmTrainPlan fm_train_plan(int64_t M, int k) {
+  FmTrainPlan p;
+  p.off_dE = 0;
+  p.off_dw = M * k;
+  p.off_scal = p.off_dw + M;
+  p.off_touch = p.off_scal + kScalFloats;
+  p.bytes = (size_t)p.off_touch * 4 + (((size_t)M + 255) & ~size_t(255));
+  return p;
 }
 
 // ---------------------------------------------------------------------------
@@ -373,7 +454,7 @@ __global__ __launch_bounds__(256) void row_sums(const float* __restrict__ GT, in
 
 // Concat projection, forward and backward (DFM.py:109-137, l2_loss), wave
 // per row; each lane keeps its columns' dWp partials over the block's rows.
-// scal[0] += dbp  scal[1] += (out − y)²/2
+// scal[kScalBiasGrad] += dbp  scal[kScalDataLoss] += (out − y)²/2
 __global__ __launch_bounds__(256) void dfm_train_head(
     const int32_t* __restrict__ idx, const float* __restrict__ y, int64_t B, int F,
     const float* __restrict__ E, const float* __restrict__ w, int64_t M, int k,
@@ -437,8 +518,8 @@ __global__ __launch_bounds__(256) void dfm_train_head(
     if (c < D && part[j] != 0.f) atomicAdd(&dWp[c], part[j]);
   }
   if (l == 0) {   // (g is wave-uniform: every lane holds the same sums)
-    atomicAdd(&scal[0], sb);
-    atomicAdd(&scal[1], sl);
+    atomicAdd(&scal[kScalBiasGrad], sb);
+    atomicAdd(&scal[kScalDataLoss], sl);
   }
 }
 
@@ -466,7 +547,37 @@ __global__ __launch_bounds__(256) void dfm_train_scatter(
   }
 }
 
-struct DfmTrainPlan {
+// The DeepFM / AFM workspace allocator and the part of the layout the two
+// plans share.  Offsets are in floats, every region rounded up to 64 floats.
+// The persistent prefix comes first, at offsets independent of B:
+//   scal | dE [M·k] | dw [M] | the model's own dense gradients | touched [M bytes]
+// all zero-initialised and kept zeroed by the step (but Adam's β powers in
+// scal), so a workspace grown for a larger batch keeps its state by copying the
+// old one's first `state` floats, and a smaller batch finds every buffer the
+// step accumulates into where the last step left it zeroed.  What follows is
+// per-batch scratch that a step writes before it reads it, so it may move
+// with B.
+struct TrainWs {
+  int64_t off_scal, off_dE, off_dw, off_touch;
+  int64_t state;   // floats of the persistent prefix
+  int64_t total;   // floats allocated so far
+  int64_t take(int64_t n) {
+    const int64_t r = total;
+    total += (n + 63) & ~int64_t(63);
+    return r;
+  }
+  void take_state_head(int64_t M, int k) {
+    off_scal = take(kScalFloats);
+    off_dE = take(M * k);
+    off_dw = take(M);
+  }
+  void take_state_tail(int64_t M) {
+    off_touch = take((M + 3) / 4);
+    state = total;
+  }
+};
+
+struct DfmTrainPlan : TrainWs {
   int64_t Bp;
   int L, D0;
   int d[kDfmTrainMaxLayers + 1];     // d[0] = F·k, d[l+1] = layer l width
@@ -474,8 +585,7 @@ struct DfmTrainPlan {
   int64_t off_dW[kDfmTrainMaxLayers], off_db[kDfmTrainMaxLayers];
   int64_t off_H[kDfmTrainMaxLayers + 1], off_HT[kDfmTrainMaxLayers];
   int64_t off_G[kDfmTrainMaxLayers + 1], off_GT[kDfmTrainMaxLayers + 1];
-  int64_t off_dX0, off_g, off_dWp, off_dE, off_dw, off_scal, off_touch;
-  int64_t total;   // floats
+  int64_t off_dX0, off_g, off_dWp;
 };
 
 static bool dfm_train_plan(int64_t B, int F, int k, int64_t M, int L, const int32_t* dims,
@@ -491,34 +601,24 @@ static bool dfm_train_plan(int64_t B, int F, int k, int64_t M, int L, const int3
   }
   if (F + k + p.d[L] > kDfmHeadMaxCols) return false;
   p.Bp = pad8(B > 0 ? B : 1);
-  int64_t o = 0;
-  auto take = [&](int64_t n) { const int64_t r = o; o += (n + 63) & ~int64_t(63); return r; };
-  // zero-initialised, kept zeroed by the step (scalars incl. Adam's β powers,
-  // dE, dw, dWp, touched mask): first, at B-independent offsets, so a workspace
-  // grown for a larger batch keeps its state by copying the old one's bytes
-  // and a smaller batch finds every buffer the step accumulates into where the
-  // last step left it zeroed (what follows the prefix is per-batch scratch
-  // that a step writes before it reads it, so it may move with B)
-  p.off_scal = take(16);
-  p.off_dE = take(M * k);
-  p.off_dw = take(M);
-  p.off_dWp = take(F + k + p.d[L]);
-  p.off_touch = take((M + 3) / 4);   // touched-row mask, M bytes
+  p.take_state_head(M, k);
+  p.off_dWp = p.take(F + k + p.d[L]);
+  p.take_state_tail(M);
+  // per-batch scratch (dW / db are written by the step before the optimizer reads them)
   for (int i = 0; i < L; ++i) {
-    p.off_WtP[i] = take((int64_t)p.d[i + 1] * pad8(p.d[i]));
-    p.off_WP[i] = take((int64_t)p.d[i] * pad8(p.d[i + 1]));
-    p.off_dW[i] = take((int64_t)p.d[i] * p.d[i + 1]);
-    p.off_db[i] = take(p.d[i + 1]);
-    p.off_HT[i] = take((int64_t)p.d[i] * p.Bp);
+    p.off_WtP[i] = p.take((int64_t)p.d[i + 1] * pad8(p.d[i]));
+    p.off_WP[i] = p.take((int64_t)p.d[i] * pad8(p.d[i + 1]));
+    p.off_dW[i] = p.take((int64_t)p.d[i] * p.d[i + 1]);
+    p.off_db[i] = p.take(p.d[i + 1]);
+    p.off_HT[i] = p.take((int64_t)p.d[i] * p.Bp);
   }
   for (int i = 1; i <= L; ++i) {
-    p.off_H[i] = take(p.Bp * pad8(p.d[i]));
-    p.off_G[i] = take(p.Bp * pad8(p.d[i]));
-    p.off_GT[i] = take((int64_t)p.d[i] * p.Bp);
+    p.off_H[i] = p.take(p.Bp * pad8(p.d[i]));
+    p.off_G[i] = p.take(p.Bp * pad8(p.d[i]));
+    p.off_GT[i] = p.take((int64_t)p.d[i] * p.Bp);
   }
-  p.off_dX0 = take(p.Bp * p.D0);
-  p.off_g = take(p.Bp);
-  p.total = o;
+  p.off_dX0 = p.take(p.Bp * p.D0);
+  p.off_g = p.take(p.Bp);
   return true;
 }
 
@@ -680,8 +780,8 @@ __global__ __launch_bounds__(256) void afm_train_head(
     if (c < A && accB[j] != 0.f) atomicAdd(&db[c], accB[j]);
   }
   if (l == 0) {   // g is wave-uniform
-    atomicAdd(&scal[0], sg);
-    atomicAdd(&scal[1], sl);
+    atomicAdd(&scal[kScalBiasGrad], sg);
+    atomicAdd(&scal[kScalDataLoss], sl);
   }
 }
 
@@ -744,13 +844,12 @@ __global__ __launch_bounds__(256) void sum_splits(const float* __restrict__ part
   }
 }
 
-struct AfmTrainPlan {
+struct AfmTrainPlan : TrainWs {
   int np;
   int64_t n, Kp;
   int S;
   int64_t off_Wt, off_R, off_Gz, off_T, off_DP, off_att, off_g, off_part;
-  int64_t off_dE, off_dw, off_dW, off_db, off_dpv, off_dP, off_scal, off_touch;
-  int64_t total;   // floats
+  int64_t off_dW, off_db, off_dpv, off_dP;
 };
 
 static bool afm_train_plan(int64_t B, int F, int k, int A, int64_t M, AfmTrainPlan& p) {
@@ -763,28 +862,45 @@ static bool afm_train_plan(int64_t B, int F, int k, int A, int64_t M, AfmTrainPl
   if (p.n > (int64_t)1 << 30) return false;
   p.Kp = pad8(p.n > 0 ? p.n : 1);
   p.S = (int)((p.Kp + kAfmSplitK - 1) / kAfmSplitK);
-  int64_t o = 0;
-  auto take = [&](int64_t n) { const int64_t r = o; o += (n + 63) & ~int64_t(63); return r; };
-  // zero-initialised, kept zeroed by the step; first, at B-independent
-  // offsets (see dfm_train_plan)
-  p.off_scal = take(16);
-  p.off_dE = take(M * k);
-  p.off_dw = take(M);
-  p.off_dW = take((int64_t)k * A);
-  p.off_db = take(A);
-  p.off_dpv = take(A);
-  p.off_dP = take(k);
-  p.off_touch = take((M + 3) / 4);   // touched-row mask, M bytes
-  p.off_Wt = take((int64_t)A * k);
-  p.off_R = take(p.n * A);
-  p.off_Gz = take(p.n * A);
-  p.off_T = take((int64_t)(k + A) * p.Kp);   // PT [k][Kp] then GzT [A][Kp]
-  p.off_DP = take(p.n * k);
-  p.off_att = take(p.n);
-  p.off_g = take(B);
-  p.off_part = take((int64_t)p.S * k * A);
-  p.total = o;
+  p.take_state_head(M, k);
+  p.off_dW = p.take((int64_t)k * A);
+  p.off_db = p.take(A);
+  p.off_dpv = p.take(A);
+  p.off_dP = p.take(k);
+  p.take_state_tail(M);
+  // per-batch scratch
+  p.off_Wt = p.take((int64_t)A * k);
+  p.off_R = p.take(p.n * A);
+  p.off_Gz = p.take(p.n * A);
+  p.off_T = p.take((int64_t)(k + A) * p.Kp);   // PT [k][Kp] then GzT [A][Kp]
+  p.off_DP = p.take(p.n * k);
+  p.off_att = p.take(p.n);
+  p.off_g = p.take(B);
+  p.off_part = p.take((int64_t)p.S * k * A);
   return true;
+}
+
+// tr_pad over src [R][C] (row stride lds): dst [C][ldd], rows R..Rp zero
+static void launch_tr_pad(float* src, int64_t R, int C, int64_t lds, const float* H, int64_t ldh,
+                          float* dst, int64_t ldd, int64_t Rp, hipStream_t st) {
+  hipLaunchKernelGGL(tr_pad, dim3((unsigned)((Rp + 31) / 32), (unsigned)((C + 31) / 32)),
+                     dim3(256), 0, st, src, R, C, lds, H, ldh, dst, ldd, Rp);
+}
+
+// C [M][ldc] = A [M][lda] · Btᵀ, Bt [N][ldb]; the callers add what else they need
+static GemmArgs gemm_plain(int64_t M, int N, int64_t K, const void* A, int64_t lda,
+                           const void* Bt, int64_t ldb, void* C, int64_t ldc) {
+  GemmArgs g{};
+  g.M = M;
+  g.N = N;
+  g.K = (int)K;
+  g.A = A;
+  g.lda = lda;
+  g.Bt = Bt;
+  g.ldb = ldb;
+  g.C = C;
+  g.ldc = ldc;
+  return g;
 }
 
 }  // namespace hhfm
@@ -792,10 +908,7 @@ static bool afm_train_plan(int64_t B, int F, int k, int A, int64_t M, AfmTrainPl
 using namespace hhfm;
 
 extern "C" size_t hhfm_train_workspace(int64_t features_M, int32_t k) {
-  // dE [M*k] + dw [M] + 16 scalars + the touched-row mask [M] bytes; must be
-  // zero-filled once by the caller
-  return (size_t)features_M * k * 4 + (size_t)features_M * 4 + 64 +
-         (((size_t)features_M + 255) & ~size_t(255));
+  return fm_train_plan(features_M, k).bytes;
 }
 
 extern "C" int hhfm_fm_train_step(const int32_t* idx, const float* y, int64_t B, int32_t F,
@@ -807,32 +920,25 @@ extern "C" int hhfm_fm_train_step(const int32_t* idx, const float* y, int64_t B,
   if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
   if (!E || !w || !w0 || !loss || !workspace) return HHFM_EINVAL;
   if (B > 0 && (!idx || !y)) return HHFM_EINVAL;   // an empty batch reads no rows
-  if (optimizer != OPT_SGD && (!accE || !accw || !accw0)) return HHFM_EINVAL;
-  if (ws_bytes < hhfm_train_workspace(features_M, k)) return HHFM_EWORKSPACE;
+  float* const acc[] = {accE, accw, accw0};
+  if (!slots_ok(optimizer, acc, 3)) return HHFM_EINVAL;
+  const FmTrainPlan p = fm_train_plan(features_M, k);
+  if (ws_bytes < p.bytes) return HHFM_EWORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  float* dE = reinterpret_cast<float*>(workspace);
-  float* dw = dE + features_M * k;
-  float* scal = dw + features_M;
-  uint8_t* touched = reinterpret_cast<uint8_t*>(scal + 16);
+  float* ws = reinterpret_cast<float*>(workspace);
+  float* scal = ws + p.off_scal;
   if (B > 0)
     hipLaunchKernelGGL(fm_train_rows, dim3(grid_for_n(B * 64)), dim3(256), 0, st, idx, y, B, F,
-                       E, w, w0, features_M, k, dE, dw, scal);
+                       E, w, w0, features_M, k, ws + p.off_dE, ws + p.off_dw, scal);
   // sparse gradients (FM.py:123-126): w's always (embedding_lookup only), E's
   // when λ = 0 (no dense l2 term); w0 and the λ > 0 table are dense
-  const bool mark = optimizer == OPT_MOMENTUM && B > 0;
-  if (mark)
-    hipLaunchKernelGGL(mark_rows, dim3(grid_for_n(B * F)), dim3(256), 0, st, idx, B * F,
-                       features_M, touched, (uint8_t)1);
-  const int64_t nE = features_M * k;
-  apply_opt(E, dE, accE, nE, lam, optimizer, lr, scal + 8, touched, k, lam == 0.f, scal + 2, st);
-  apply_opt(w, dw, accw, features_M, 0.f, optimizer, lr, scal + 8, touched, 1, true, nullptr, st);
-  apply_opt(w0, scal, accw0, 1, 0.f, optimizer, lr, scal + 8, nullptr, 1, false, nullptr, st);
-  if (mark)
-    hipLaunchKernelGGL(mark_rows, dim3(grid_for_n(B * F)), dim3(256), 0, st, idx, B * F,
-                       features_M, touched, (uint8_t)0);
-  if (optimizer == OPT_ADAM) hipLaunchKernelGGL(adam_advance, dim3(1), dim3(1), 0, st, scal + 8);
-  hipLaunchKernelGGL(finish_loss, dim3(1), dim3(1), 0, st, scal, lam, loss);
-  return (int)hipGetLastError();
+  const OptVar vars[] = {
+      {E, ws + p.off_dE, accE, features_M * k, lam, k, lam == 0.f, true},
+      {w, ws + p.off_dw, accw, features_M, 0.f, 1, true, false},
+      {w0, scal + kScalBiasGrad, accw0, 1, 0.f, 1, false, false}};
+  uint8_t* touched = reinterpret_cast<uint8_t*>(ws + p.off_touch);
+  return optimizer_tail(vars, (int)std::size(vars), {{idx, B * F}}, features_M, optimizer, lr,
+                        scal, touched, lam, loss, st);
 }
 
 extern "C" int hhfm_hhfm_train_step(const int32_t* X, const int32_t* Neg, int64_t B,
@@ -846,36 +952,21 @@ extern "C" int hhfm_hhfm_train_step(const int32_t* X, const int32_t* Neg, int64_
   if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
   if (!E || !loss || !workspace) return HHFM_EINVAL;
   if (B > 0 && (!X || !Neg)) return HHFM_EINVAL;
-  if (optimizer != OPT_SGD && !accE) return HHFM_EINVAL;
-  if (ws_bytes < hhfm_train_workspace(features_M, k)) return HHFM_EWORKSPACE;
+  if (!slots_ok(optimizer, &accE, 1)) return HHFM_EINVAL;
+  const FmTrainPlan p = fm_train_plan(features_M, k);   // dw stays unused
+  if (ws_bytes < p.bytes) return HHFM_EWORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  float* dE = reinterpret_cast<float*>(workspace);
-  float* scal = dE + features_M * k + features_M;
-  uint8_t* touched = reinterpret_cast<uint8_t*>(scal + 16);
+  float* ws = reinterpret_cast<float*>(workspace);
+  float* scal = ws + p.off_scal;
   if (B > 0)
     hipLaunchKernelGGL(hhfm_train_rows, dim3(grid_for_n(B * 64)), dim3(256), 0, st, X, Neg, B,
                        ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E, features_M, k,
-                       dE, scal);
+                       ws + p.off_dE, scal);
   // E's gradient is dense through λ·l2(E) (OurModel7.py:180-184), sparse at λ = 0
-  const bool sparseE = lam == 0.f;
-  const bool mark = optimizer == OPT_MOMENTUM && sparseE && B > 0;
-  if (mark) {
-    hipLaunchKernelGGL(mark_rows, dim3(grid_for_n(B * ncols)), dim3(256), 0, st, X, B * ncols,
-                       features_M, touched, (uint8_t)1);
-    hipLaunchKernelGGL(mark_rows, dim3(grid_for_n(B * NG)), dim3(256), 0, st, Neg, B * NG,
-                       features_M, touched, (uint8_t)1);
-  }
-  const int64_t nE = features_M * k;
-  apply_opt(E, dE, accE, nE, lam, optimizer, lr, scal + 8, touched, k, sparseE, scal + 2, st);
-  if (mark) {
-    hipLaunchKernelGGL(mark_rows, dim3(grid_for_n(B * ncols)), dim3(256), 0, st, X, B * ncols,
-                       features_M, touched, (uint8_t)0);
-    hipLaunchKernelGGL(mark_rows, dim3(grid_for_n(B * NG)), dim3(256), 0, st, Neg, B * NG,
-                       features_M, touched, (uint8_t)0);
-  }
-  if (optimizer == OPT_ADAM) hipLaunchKernelGGL(adam_advance, dim3(1), dim3(1), 0, st, scal + 8);
-  hipLaunchKernelGGL(finish_loss, dim3(1), dim3(1), 0, st, scal, lam, loss);
-  return (int)hipGetLastError();
+  const OptVar vars[] = {{E, ws + p.off_dE, accE, features_M * k, lam, k, lam == 0.f, true}};
+  uint8_t* touched = reinterpret_cast<uint8_t*>(ws + p.off_touch);
+  return optimizer_tail(vars, (int)std::size(vars), {{X, B * ncols}, {Neg, B * NG}}, features_M,
+                        optimizer, lr, scal, touched, lam, loss, st);
 }
 
 extern "C" int hhfm_dfm_train_workspace(int64_t B, int32_t F, int32_t k, int64_t features_M,
@@ -890,7 +981,7 @@ extern "C" int hhfm_dfm_train_workspace(int64_t B, int32_t F, int32_t k, int64_t
 }
 
 // bytes at the front of the DeepFM workspace that carry state between steps
-// (scalars incl. Adam's β powers, dE, dw, dWp, the touched mask); B-independent
+// (TrainWs's persistent prefix); B-independent
 extern "C" int hhfm_dfm_train_state_bytes(int32_t F, int32_t k, int64_t features_M,
                                           int32_t nlayers, const int32_t* layer_dims,
                                           size_t* state_bytes) {
@@ -898,7 +989,7 @@ extern "C" int hhfm_dfm_train_state_bytes(int32_t F, int32_t k, int64_t features
   if (!state_bytes || !layer_dims || features_M < 1 ||
       !dfm_train_plan(1, F, k, features_M, nlayers, layer_dims, p))
     return HHFM_EINVAL;
-  *state_bytes = (size_t)p.off_WtP[0] * 4;
+  *state_bytes = (size_t)p.state * 4;
   return HHFM_OK;
 }
 
@@ -919,54 +1010,37 @@ extern "C" int hhfm_dfm_train_step(const int32_t* idx, const float* y, int64_t B
   const int L = p.L;
   for (int i = 0; i < L; ++i)
     if (!W[i] || !bias[i]) return HHFM_EINVAL;
-  if (optimizer != OPT_SGD) {   // acc: E, w, W_0..W_{L-1}, b_0..b_{L-1}, Wp, bp
-    if (!acc) return HHFM_EINVAL;
-    for (int i = 0; i < 2 * L + 4; ++i)
-      if (!acc[i]) return HHFM_EINVAL;
-  }
+  // acc: E, w, W_0..W_{L-1}, b_0..b_{L-1}, Wp, bp
+  if (!slots_ok(optimizer, acc, 2 * L + 4)) return HHFM_EINVAL;
   if (ws_bytes < (size_t)p.total * 4) return HHFM_EWORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   float* ws = reinterpret_cast<float*>(workspace);
   auto at = [&](int64_t off) { return ws + off; };
   float* scal = at(p.off_scal);
   const int64_t Bp = p.Bp;
-  const int64_t nE = features_M * k;
-  auto acc_of = [&](int i) { return optimizer != OPT_SGD ? acc[i] : (float*)nullptr; };
-  uint8_t* touched = reinterpret_cast<uint8_t*>(at(p.off_touch));
 
   if (B > 0) {
     // weights: Wᵀ zero-padded (forward Bt) and W zero-padded (backward Bt)
     for (int i = 0; i < L; ++i) {
       const int din = p.d[i], dout = p.d[i + 1];
-      hipLaunchKernelGGL(tr_pad, dim3((unsigned)((din + 31) / 32), (unsigned)((dout + 31) / 32)),
-                         dim3(256), 0, st, W[i], (int64_t)din, dout, (int64_t)dout,
-                         (const float*)nullptr, (int64_t)0, at(p.off_WtP[i]), pad8(din),
-                         pad8(din));
+      launch_tr_pad(W[i], din, dout, dout, nullptr, 0, at(p.off_WtP[i]), pad8(din), pad8(din), st);
       hipLaunchKernelGGL(copy_pad, dim3(grid_for_n((int64_t)din * pad8(dout))), dim3(256), 0, st,
                          W[i], (int64_t)din, dout, at(p.off_WP[i]), (int)pad8(dout));
     }
     // forward: H_{i+1} = relu(H_i · W_i + b_i), H_0 gathered from the table
     for (int i = 0; i < L; ++i) {
-      GemmArgs g{};
-      g.M = B;
-      g.N = p.d[i + 1];
-      g.K = p.d[i];
+      GemmArgs g = gemm_plain(B, p.d[i + 1], p.d[i], i ? at(p.off_H[i]) : nullptr,
+                              i ? pad8(p.d[i]) : 0, at(p.off_WtP[i]), pad8(p.d[i]),
+                              at(p.off_H[i + 1]), pad8(p.d[i + 1]));
       if (i == 0) {
         g.gidx = idx;
         g.T = E;
         g.Mtab = features_M;
         g.F = F;
         g.kf = k;
-      } else {
-        g.A = at(p.off_H[i]);
-        g.lda = pad8(p.d[i]);
       }
-      g.Bt = at(p.off_WtP[i]);
-      g.ldb = pad8(p.d[i]);
       g.bias = bias[i];
       g.relu = 1;
-      g.C = at(p.off_H[i + 1]);
-      g.ldc = pad8(p.d[i + 1]);
       launch_gemm(g, false, 0, st);
     }
     // head: out, d = out − y, dWp, dbp, dw, last layer's delta
@@ -975,9 +1049,7 @@ extern "C" int hhfm_dfm_train_step(const int32_t* idx, const float* y, int64_t B
     hipLaunchKernelGGL(dfm_train_head, dim3(grid_for_n(B * 64 / 8)), dim3(256), 0, st, idx, y, B,
                        F, E, w, features_M, k, at(p.off_H[L]), p.d[L], ldL, Wp, bp, at(p.off_G[L]),
                        at(p.off_g), at(p.off_dWp), at(p.off_dw), scal);
-    hipLaunchKernelGGL(tr_pad, dim3((unsigned)((Bp + 31) / 32), (unsigned)((p.d[L] + 31) / 32)),
-                       dim3(256), 0, st, at(p.off_G[L]), B, p.d[L], ldL, (const float*)nullptr,
-                       (int64_t)0, at(p.off_GT[L]), Bp, Bp);
+    launch_tr_pad(at(p.off_G[L]), B, p.d[L], ldL, nullptr, 0, at(p.off_GT[L]), Bp, Bp, st);
     // backward through the layers
     for (int i = L - 1; i >= 0; --i) {
       const int din = p.d[i], dout = p.d[i + 1];
@@ -986,78 +1058,49 @@ extern "C" int hhfm_dfm_train_step(const int32_t* idx, const float* y, int64_t B
         hipLaunchKernelGGL(gather_tr, dim3((unsigned)((Bp + 31) / 32), (unsigned)((din + 31) / 32)),
                            dim3(256), 0, st, idx, B, F, E, features_M, k, at(p.off_HT[0]), Bp);
       else
-        hipLaunchKernelGGL(tr_pad, dim3((unsigned)((Bp + 31) / 32), (unsigned)((din + 31) / 32)),
-                           dim3(256), 0, st, at(p.off_H[i]), B, din, pad8(din),
-                           (const float*)nullptr, (int64_t)0, at(p.off_HT[i]), Bp, Bp);
-      {   // dW_i = H_iᵀ · G_{i+1}
-        GemmArgs g{};
-        g.M = din;
-        g.N = dout;
-        g.K = (int)Bp;
-        g.A = at(p.off_HT[i]);
-        g.lda = Bp;
-        g.Bt = at(p.off_GT[i + 1]);
-        g.ldb = Bp;
-        g.C = at(p.off_dW[i]);
-        g.ldc = dout;
-        launch_gemm(g, false, 0, st);
-      }
+        launch_tr_pad(at(p.off_H[i]), B, din, pad8(din), nullptr, 0, at(p.off_HT[i]), Bp, Bp, st);
+      // dW_i = H_iᵀ · G_{i+1}
+      launch_gemm(gemm_plain(din, dout, Bp, at(p.off_HT[i]), Bp, at(p.off_GT[i + 1]), Bp,
+                             at(p.off_dW[i]), dout),
+                  false, 0, st);
       hipLaunchKernelGGL(row_sums, dim3((unsigned)((dout + 3) / 4)), dim3(256), 0, st,
                          at(p.off_GT[i + 1]), dout, Bp, Bp, at(p.off_db[i]));
-      {   // G_i = (G_{i+1} · W_iᵀ) ⊙ relu'(H_i), or dX0 = G_1 · W_0ᵀ
-        GemmArgs g{};
-        g.M = B;
-        g.N = din;
-        g.K = dout;
-        g.A = at(p.off_G[i + 1]);
-        g.lda = pad8(dout);
-        g.Bt = at(p.off_WP[i]);
-        g.ldb = pad8(dout);
-        g.C = i == 0 ? at(p.off_dX0) : at(p.off_G[i]);
-        g.ldc = i == 0 ? p.D0 : pad8(din);
-        launch_gemm(g, false, 0, st);
-      }
+      // G_i = (G_{i+1} · W_iᵀ) ⊙ relu'(H_i), or dX0 = G_1 · W_0ᵀ
+      launch_gemm(gemm_plain(B, din, dout, at(p.off_G[i + 1]), pad8(dout), at(p.off_WP[i]),
+                             pad8(dout), i == 0 ? at(p.off_dX0) : at(p.off_G[i]),
+                             i == 0 ? p.D0 : pad8(din)),
+                  false, 0, st);
       if (i > 0)
-        hipLaunchKernelGGL(tr_pad, dim3((unsigned)((Bp + 31) / 32), (unsigned)((din + 31) / 32)),
-                           dim3(256), 0, st, at(p.off_G[i]), B, din, pad8(din),
-                           (const float*)at(p.off_H[i]), pad8(din), at(p.off_GT[i]), Bp, Bp);
+        launch_tr_pad(at(p.off_G[i]), B, din, pad8(din), at(p.off_H[i]), pad8(din),
+                      at(p.off_GT[i]), Bp, Bp, st);
     }
     hipLaunchKernelGGL(dfm_train_scatter, dim3(grid_for_n(B * 64)), dim3(256), 0, st, idx, B, F,
                        E, features_M, k, at(p.off_dX0), at(p.off_g), Wp, at(p.off_dE));
   }
   // optimizer: λ only on the layer weights and the concat projection
   // (DFM.py:146-152); the table and w have IndexedSlices gradients (sparse)
-  const bool mark = optimizer == OPT_MOMENTUM && B > 0;
-  if (mark)
-    hipLaunchKernelGGL(mark_rows, dim3(grid_for_n(B * F)), dim3(256), 0, st, idx, B * F,
-                       features_M, touched, (uint8_t)1);
-  const float* pw = scal + 8;
-  apply_opt(E, at(p.off_dE), acc_of(0), nE, 0.f, optimizer, lr, pw, touched, k, true, nullptr,
-            st);
-  apply_opt(w, at(p.off_dw), acc_of(1), features_M, 0.f, optimizer, lr, pw, touched, 1, true,
-            nullptr, st);
-  if (mark)
-    hipLaunchKernelGGL(mark_rows, dim3(grid_for_n(B * F)), dim3(256), 0, st, idx, B * F,
-                       features_M, touched, (uint8_t)0);
+  OptVar vars[2 * kDfmTrainMaxLayers + 4];
+  int nv = 0;
+  vars[nv++] = {E, at(p.off_dE), slot_of(optimizer, acc, 0), features_M * k, 0.f, k, true, false};
+  vars[nv++] = {w, at(p.off_dw), slot_of(optimizer, acc, 1), features_M, 0.f, 1, true, false};
   for (int i = 0; i < L; ++i) {
     const int64_t n = (int64_t)p.d[i] * p.d[i + 1];
-    if (B == 0) {
+    if (B == 0) {   // no backward pass wrote this batch's dW / db
       (void)hipMemsetAsync(at(p.off_dW[i]), 0, n * 4, st);
       (void)hipMemsetAsync(at(p.off_db[i]), 0, p.d[i + 1] * 4, st);
     }
-    apply_opt(W[i], at(p.off_dW[i]), acc_of(2 + i), n, lambda_l2, optimizer, lr, pw, nullptr, 1,
-              false, scal + 2, st);
-    apply_opt(bias[i], at(p.off_db[i]), acc_of(2 + L + i), (int64_t)p.d[i + 1], 0.f, optimizer,
-              lr, pw, nullptr, 1, false, nullptr, st);
+    vars[nv++] = {W[i], at(p.off_dW[i]), slot_of(optimizer, acc, 2 + i), n, lambda_l2, 1, false,
+                  true};
+    vars[nv++] = {bias[i], at(p.off_db[i]), slot_of(optimizer, acc, 2 + L + i), p.d[i + 1], 0.f,
+                  1, false, false};
   }
-  const int64_t nWp = F + k + p.d[L];
-  apply_opt(Wp, at(p.off_dWp), acc_of(2 + 2 * L), nWp, lambda_l2, optimizer, lr, pw, nullptr, 1,
-            false, scal + 2, st);
-  apply_opt(bp, scal, acc_of(3 + 2 * L), 1, 0.f, optimizer, lr, pw, nullptr, 1, false, nullptr,
-            st);
-  if (optimizer == OPT_ADAM) hipLaunchKernelGGL(adam_advance, dim3(1), dim3(1), 0, st, scal + 8);
-  hipLaunchKernelGGL(finish_loss, dim3(1), dim3(1), 0, st, scal, lambda_l2, loss);
-  return (int)hipGetLastError();
+  vars[nv++] = {Wp, at(p.off_dWp), slot_of(optimizer, acc, 2 + 2 * L), F + k + p.d[L], lambda_l2,
+                1, false, true};
+  vars[nv++] = {bp, scal + kScalBiasGrad, slot_of(optimizer, acc, 3 + 2 * L), 1, 0.f, 1, false,
+                false};
+  uint8_t* touched = reinterpret_cast<uint8_t*>(at(p.off_touch));
+  return optimizer_tail(vars, nv, {{idx, B * F}}, features_M, optimizer, lr, scal, touched,
+                        lambda_l2, loss, st);
 }
 
 extern "C" int hhfm_afm_train_workspace(int64_t B, int32_t F, int32_t k, int32_t A,
@@ -1073,7 +1116,7 @@ extern "C" int hhfm_afm_train_state_bytes(int32_t F, int32_t k, int32_t A, int64
                                           size_t* state_bytes) {
   AfmTrainPlan p;
   if (!state_bytes || !afm_train_plan(1, F, k, A, features_M, p)) return HHFM_EINVAL;
-  *state_bytes = (size_t)p.off_Wt * 4;
+  *state_bytes = (size_t)p.state * 4;
   return HHFM_OK;
 }
 
@@ -1088,11 +1131,7 @@ extern "C" int hhfm_afm_train_step(const int32_t* idx, const float* y, int64_t B
   if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
   if (!E || !w || !w0 || !W || !b || !pvec || !P || !loss || !workspace) return HHFM_EINVAL;
   if (B > 0 && (!idx || !y)) return HHFM_EINVAL;
-  if (optimizer != OPT_SGD) {   // acc: E, w, w0, W, b, pvec, P
-    if (!acc) return HHFM_EINVAL;
-    for (int i = 0; i < 7; ++i)
-      if (!acc[i]) return HHFM_EINVAL;
-  }
+  if (!slots_ok(optimizer, acc, 7)) return HHFM_EINVAL;   // acc: E, w, w0, W, b, pvec, P
   if (ws_bytes < (size_t)p.total * 4) return HHFM_EWORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   float* ws = reinterpret_cast<float*>(workspace);
@@ -1100,19 +1139,12 @@ extern "C" int hhfm_afm_train_step(const int32_t* idx, const float* y, int64_t B
   float* scal = at(p.off_scal);
   float* PT = at(p.off_T);
   float* GzT = PT + (int64_t)k * p.Kp;
-  auto acc_of = [&](int i) { return optimizer != OPT_SGD ? acc[i] : (float*)nullptr; };
-  uint8_t* touched = reinterpret_cast<uint8_t*>(at(p.off_touch));
 
   if (B > 0) {
     // Wᵀ [A][k] for the forward GEMM
-    hipLaunchKernelGGL(tr_pad, dim3((unsigned)((k + 31) / 32), (unsigned)((A + 31) / 32)),
-                       dim3(256), 0, st, W, (int64_t)k, A, (int64_t)A, (const float*)nullptr,
-                       (int64_t)0, at(p.off_Wt), (int64_t)k, (int64_t)k);
+    launch_tr_pad(W, k, A, A, nullptr, 0, at(p.off_Wt), k, k, st);
     {   // R = relu(pairs · W + b)   (AFM.py:117-121)
-      GemmArgs g{};
-      g.M = p.n;
-      g.N = A;
-      g.K = k;
+      GemmArgs g = gemm_plain(p.n, A, k, nullptr, 0, at(p.off_Wt), k, at(p.off_R), A);
       g.pair_mode = 1;
       g.P = p.np;
       g.gidx = idx;
@@ -1120,12 +1152,8 @@ extern "C" int hhfm_afm_train_step(const int32_t* idx, const float* y, int64_t B
       g.Mtab = features_M;
       g.F = F;
       g.kf = k;
-      g.Bt = at(p.off_Wt);
-      g.ldb = k;
       g.bias = b;
       g.relu = 1;
-      g.C = at(p.off_R);
-      g.ldc = A;
       launch_gemm(g, false, 0, st);
     }
     // a few rows per wave: the per-wave dP / dp / db flush is k + 2A same-address atomics
@@ -1137,30 +1165,10 @@ extern "C" int hhfm_afm_train_step(const int32_t* idx, const float* y, int64_t B
     if (p.Kp > p.n)
       hipLaunchKernelGGL(zero_cols, dim3(grid_for_n((int64_t)(k + A) * (p.Kp - p.n))),
                          dim3(256), 0, st, PT, k + A, p.Kp, p.n);
-    {   // DP = dZ · Wᵀ   (Bt = W [k][A])
-      GemmArgs g{};
-      g.M = p.n;
-      g.N = k;
-      g.K = A;
-      g.A = at(p.off_Gz);
-      g.lda = A;
-      g.Bt = W;
-      g.ldb = A;
-      g.C = at(p.off_DP);
-      g.ldc = k;
-      launch_gemm(g, false, 0, st);
-    }
+    // DP = dZ · Wᵀ   (Bt = W [k][A])
+    launch_gemm(gemm_plain(p.n, k, A, at(p.off_Gz), A, W, A, at(p.off_DP), k), false, 0, st);
     {   // dW = pairsᵀ · dZ, split over the combos
-      GemmArgs g{};
-      g.M = k;
-      g.N = A;
-      g.K = (int)p.Kp;
-      g.A = PT;
-      g.lda = p.Kp;
-      g.Bt = GzT;
-      g.ldb = p.Kp;
-      g.C = at(p.off_part);
-      g.ldc = A;
+      GemmArgs g = gemm_plain(k, A, p.Kp, PT, p.Kp, GzT, p.Kp, at(p.off_part), A);
       g.ksplit = kAfmSplitK;
       g.cz_stride = (int64_t)k * A;
       launch_gemm(g, false, 0, st);
@@ -1173,29 +1181,17 @@ extern "C" int hhfm_afm_train_step(const int32_t* idx, const float* y, int64_t B
   }
   // the table and w have IndexedSlices gradients (sparse); l2_regularizer(λ)
   // on attention_W only (AFM.py:146)
-  const bool mark = optimizer == OPT_MOMENTUM && B > 0;
-  if (mark)
-    hipLaunchKernelGGL(mark_rows, dim3(grid_for_n(B * F)), dim3(256), 0, st, idx, B * F,
-                       features_M, touched, (uint8_t)1);
-  const float* pw = scal + 8;
-  const int64_t nE = features_M * k;
-  apply_opt(E, at(p.off_dE), acc_of(0), nE, 0.f, optimizer, lr, pw, touched, k, true, nullptr,
-            st);
-  apply_opt(w, at(p.off_dw), acc_of(1), features_M, 0.f, optimizer, lr, pw, touched, 1, true,
-            nullptr, st);
-  if (mark)
-    hipLaunchKernelGGL(mark_rows, dim3(grid_for_n(B * F)), dim3(256), 0, st, idx, B * F,
-                       features_M, touched, (uint8_t)0);
-  apply_opt(w0, scal, acc_of(2), 1, 0.f, optimizer, lr, pw, nullptr, 1, false, nullptr, st);
-  apply_opt(W, at(p.off_dW), acc_of(3), (int64_t)k * A, lambda_att, optimizer, lr, pw, nullptr, 1,
-            false, scal + 2, st);
-  apply_opt(b, at(p.off_db), acc_of(4), (int64_t)A, 0.f, optimizer, lr, pw, nullptr, 1, false,
-            nullptr, st);
-  apply_opt(pvec, at(p.off_dpv), acc_of(5), (int64_t)A, 0.f, optimizer, lr, pw, nullptr, 1, false,
-            nullptr, st);
-  apply_opt(P, at(p.off_dP), acc_of(6), (int64_t)k, 0.f, optimizer, lr, pw, nullptr, 1, false,
-            nullptr, st);
-  if (optimizer == OPT_ADAM) hipLaunchKernelGGL(adam_advance, dim3(1), dim3(1), 0, st, scal + 8);
-  hipLaunchKernelGGL(finish_loss, dim3(1), dim3(1), 0, st, scal, lambda_att, loss);
-  return (int)hipGetLastError();
+  auto slot = [&](int i) { return slot_of(optimizer, acc, i); };
+  const OptVar vars[] = {
+      {E, at(p.off_dE), slot(0), features_M * k, 0.f, k, true, false},
+      {w, at(p.off_dw), slot(1), features_M, 0.f, 1, true, false},
+      {w0, scal + kScalBiasGrad, slot(2), 1, 0.f, 1, false, false},
+      {W, at(p.off_dW), slot(3), (int64_t)k * A, lambda_att, 1, false, true},
+      {b, at(p.off_db), slot(4), A, 0.f, 1, false, false},
+      {pvec, at(p.off_dpv), slot(5), A, 0.f, 1, false, false},
+      {P, at(p.off_dP), slot(6), k, 0.f, 1, false, false}};
+  uint8_t* touched = reinterpret_cast<uint8_t*>(at(p.off_touch));
+  return optimizer_tail(vars, (int)std::size(vars), {{idx, B * F}}, features_M, optimizer, lr,
+                        scal, touched, lambda_att, loss, st);
 }
+

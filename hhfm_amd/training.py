@@ -22,10 +22,10 @@ from .harness import partition_all
 from ._native import native
 
 # --optimizer names (FM.py:129-136, AFM.py:151-158, OurModel7.py:186-193) -> the
-# train kernels' optimizer codes (include/hhfm.h)
+# train kernels' optimizer codes (enum hhfm_optimizer, include/hhfm.h)
 _OPT = {"AdagradOptimizer": 0, "GradientDescentOptimizer": 1, "MomentumOptimizer": 2,
         "AdamOptimizer": 3}
-_SGD = 1
+_ADAGRAD, _SGD, _MOMENTUM, _ADAM = _OPT.values()
 
 
 def _opt_code(model):
@@ -40,30 +40,33 @@ def _slots(opt, t):
     """The optimizer's slot array for variable ``t``: Adagrad's accumulator
     (TF initial_accumulator_value 0.1), Momentum's zeroed accumulator, Adam's
     zeroed m then v (2 × numel); SGD keeps none (a 1-element placeholder)."""
-    if opt == 0:
+    if opt == _ADAGRAD:
         return torch.full_like(t, 0.1)
-    if opt == 2:
+    if opt == _MOMENTUM:
         return torch.zeros_like(t)
-    if opt == 3:
+    if opt == _ADAM:
         return torch.zeros(2 * t.numel(), dtype=t.dtype, device=t.device)
     return torch.zeros(1, dtype=t.dtype, device=t.device)
 
 
-def _state(model, names, opt):
-    """Optimizer slots (``_slots``) + the zeroed gradient workspace (which also
-    carries Adam's β1^t, β2^t), created on first use."""
+def _state(model, names, opt, fixed_ws=False):
+    """The model's train state, created on first use: optimizer slots
+    (``_slots``) per variable of ``names``, ``loss``, ``opt`` and the workspace
+    ``ws`` — FM / HHFM's fixed one (``fixed_ws``; zeroed gradient buffers,
+    Adam's β1^t, β2^t), or None for ``_ensure_ws`` to size by the batch."""
     st = getattr(model, "_train_state", None)
-    if st is not None and st.get("opt") != opt:
+    if st is not None and st["opt"] != opt:
         raise ValueError("the optimizer changed after the first partial_fit")
     if st is None:
         if model.table_dtype != torch.float32:
             raise NotImplementedError("training runs on fp32 tables")
         st = {n: _slots(opt, model.weights[n]) for n in names}
         st["opt"] = opt
-        k = model.weights["feature_embeddings"].shape[1]
-        nbytes = native().train_workspace(model.features_M, k)
-        st["ws"] = torch.zeros(nbytes, dtype=torch.uint8, device=model.device)
         st["loss"] = torch.zeros(1, dtype=torch.float32, device=model.device)
+        st["ws"], st["ws_rows"] = None, 0
+        if fixed_ws:
+            M, k = model.weights["feature_embeddings"].shape
+            st["ws"] = _grow(None, native().train_workspace(M, k), 0, model.device)
         model._train_state = st
     return st
 
@@ -79,24 +82,36 @@ def _grow(old, nbytes, state_bytes, dev):
     return ws
 
 
+def _ensure_ws(st, B, dev, size_fn, state_fn):
+    """``st["ws"]`` large enough for a batch of ``B`` rows: ``size_fn(B)`` bytes,
+    the first ``state_fn()`` of them kept when it has to grow (``_grow``)."""
+    if st["ws"] is None or st["ws_rows"] < B:
+        st["ws"] = _grow(st["ws"], size_fn(B), state_fn(), dev)
+        st["ws_rows"] = B
+    return st["ws"]
+
+
+def _labels(model, data):
+    return torch.as_tensor(np.asarray(data["Y"], np.float32).reshape(-1)).to(model.device)
+
+
 def fm_partial_fit(model, data) -> float:
     """FM.partial_fit (FM.py:168-171): one optimizer step, returns the loss."""
     opt = _opt_code(model)
     if model.keep != 1:
         raise NotImplementedError("dropout keep < 1 is not implemented")
     W = model.weights
-    st = _state(model, ["feature_embeddings", "feature_bias", "bias"], opt)
+    st = _state(model, ["feature_embeddings", "feature_bias", "bias"], opt, fixed_ws=True)
     X = model._idx(data["X"])
-    y = torch.as_tensor(np.asarray(data["Y"], np.float32).reshape(-1)).to(model.device)
+    y = _labels(model, data)
     B, F = X.shape
     M, k = W["feature_embeddings"].shape
-    dev = model.device
     native().fm_train_step(X.data_ptr(), y.data_ptr(), B, F, W["feature_embeddings"].data_ptr(),
                            W["feature_bias"].data_ptr(), W["bias"].data_ptr(), M, k,
                            float(model.learning_rate), float(model.lamda_bilinear), opt,
                            st["feature_embeddings"].data_ptr(), st["feature_bias"].data_ptr(),
                            st["bias"].data_ptr(), st["ws"].data_ptr(), st["ws"].numel(),
-                           st["loss"].data_ptr(), ops._stream(dev))
+                           st["loss"].data_ptr(), ops._stream(model.device))
     return float(st["loss"].item())
 
 
@@ -105,7 +120,7 @@ def hhfm_partial_fit(model, data) -> float:
     F1 ctx columns, F2 time columns."""
     opt = _opt_code(model)
     W = model.weights
-    st = _state(model, ["feature_embeddings"], opt)
+    st = _state(model, ["feature_embeddings"], opt, fixed_ws=True)
     parts = [np.asarray(data["X"])]
     if model.context:
         parts.append(np.asarray(data["F1"]))
@@ -133,31 +148,21 @@ def dfm_partial_fit(model, data) -> float:
     L = len(model.deep_layers)
     names = (["feature_embeddings", "feature_bias"] + [f"layer_{i}" for i in range(L)]
              + [f"bias_{i}" for i in range(L)] + ["concat_projection", "concat_bias"])
-    st = getattr(model, "_train_state", None)
-    if st is None:
-        if model.table_dtype != torch.float32:
-            raise NotImplementedError("training runs on fp32 tables")
-        st = {n: _slots(0, W[n]) for n in names}
-        st["loss"] = torch.zeros(1, dtype=torch.float32, device=model.device)
-        st["ws"], st["ws_rows"] = None, 0
-        model._train_state = st
+    st = _state(model, names, _ADAGRAD)
     X = model._idx(data["X"])
-    y = torch.as_tensor(np.asarray(data["Y"], np.float32).reshape(-1)).to(model.device)
+    y = _labels(model, data)
     B, F = X.shape
     M, k = W["feature_embeddings"].shape
     dims = [int(d) for d in model.deep_layers]
     nat = native()
-    if st["ws"] is None or st["ws_rows"] < B:
-        nbytes = nat.dfm_train_workspace(B, F, k, M, dims)
-        st["ws"] = _grow(st["ws"], nbytes, nat.dfm_train_state_bytes(F, k, M, dims),
-                         model.device)
-        st["ws_rows"] = B
+    ws = _ensure_ws(st, B, model.device, lambda b: nat.dfm_train_workspace(b, F, k, M, dims),
+                    lambda: nat.dfm_train_state_bytes(F, k, M, dims))
     ptr = lambda n: W[n].data_ptr()  # noqa: E731
     nat.dfm_train_step(X.data_ptr(), y.data_ptr(), B, F, ptr("feature_embeddings"),
                        ptr("feature_bias"), M, k, dims, [ptr(f"layer_{i}") for i in range(L)],
                        [ptr(f"bias_{i}") for i in range(L)], ptr("concat_projection"),
-                       ptr("concat_bias"), float(model.learning_rate), float(model.l2_reg), 0,
-                       [st[n].data_ptr() for n in names], st["ws"].data_ptr(), st["ws"].numel(),
+                       ptr("concat_bias"), float(model.learning_rate), float(model.l2_reg),
+                       _ADAGRAD, [st[n].data_ptr() for n in names], ws.data_ptr(), ws.numel(),
                        st["loss"].data_ptr(), ops._stream(model.device))
     model._prep = None   # the scoring path's prepared (transposed / bf16) weights are stale
     return float(st["loss"].item())
@@ -172,27 +177,15 @@ def afm_partial_fit(model, data) -> float:
     W = model.weights
     names = ["feature_embeddings", "feature_bias", "bias", "attention_W", "attention_b",
              "attention_p", "prediction"]
-    st = getattr(model, "_train_state", None)
-    if st is not None and st.get("opt") != opt:
-        raise ValueError("the optimizer changed after the first partial_fit")
-    if st is None:
-        if model.table_dtype != torch.float32:
-            raise NotImplementedError("training runs on fp32 tables")
-        st = {n: _slots(opt, W[n]) for n in names}
-        st["opt"] = opt
-        st["loss"] = torch.zeros(1, dtype=torch.float32, device=model.device)
-        st["ws"], st["ws_rows"] = None, 0
-        model._train_state = st
+    st = _state(model, names, opt)
     X = model._idx(data["X"])
-    y = torch.as_tensor(np.asarray(data["Y"], np.float32).reshape(-1)).to(model.device)
+    y = _labels(model, data)
     B, F = X.shape
     M, k = W["feature_embeddings"].shape
     A = W["attention_W"].shape[1]
     nat = native()
-    if st["ws"] is None or st["ws_rows"] < B:
-        nbytes = nat.afm_train_workspace(B, F, k, A, M)
-        st["ws"] = _grow(st["ws"], nbytes, nat.afm_train_state_bytes(F, k, A, M), model.device)
-        st["ws_rows"] = B
+    ws = _ensure_ws(st, B, model.device, lambda b: nat.afm_train_workspace(b, F, k, A, M),
+                    lambda: nat.afm_train_state_bytes(F, k, A, M))
     lam = float(model.lamda_attention) if model.lamda_attention > 0 else 0.0
     ptr = lambda n: W[n].data_ptr()  # noqa: E731
     nat.afm_train_step(X.data_ptr(), y.data_ptr(), B, F, ptr("feature_embeddings"),
@@ -200,7 +193,7 @@ def afm_partial_fit(model, data) -> float:
                        ptr("attention_b"), ptr("attention_p"), ptr("prediction"),
                        float(model.learning_rate), lam, opt,
                        [st[n].data_ptr() for n in names] if opt != _SGD else [],
-                       st["ws"].data_ptr(), st["ws"].numel(), st["loss"].data_ptr(),
+                       ws.data_ptr(), ws.numel(), st["loss"].data_ptr(),
                        ops._stream(model.device))
     return float(st["loss"].item())
 
@@ -218,6 +211,16 @@ def _evaluate(tr):
             tr.evaluate_TopK(tr.data.Test_data))
 
 
+def _report_init(tr):
+    """The evaluation of the untrained model both epoch loops log first (Result == 0)."""
+    args = tr.args
+    t0 = time()
+    if args.Result == 0:
+        a1, a2, tk = _evaluate(tr)
+        _log(tr, "Dataset=%s %s Init: \t train=AUC:%.4f;test=AUC:%.4f,HR:%.4f,NDCG:%.4f,PRE:%.4f;"
+             "[%.1f s]" % (args.dataset, tr.method, a1, a2, tk[0], tk[1], tk[2], time() - t0))
+
+
 def _report(tr, head, t_epoch, t_eval0, res):
     a1, a2, tk = res
     _log(tr, "%s [%.1f s]\ttrain=AUC:%.4f;test=AUC:%.4f,HR:%.4f,NDCG:%.4f,PRE:%.4f;[%.1f s]"
@@ -230,12 +233,7 @@ def run_training(tr, negatives=2, neg_label=0, plateau=-0.0075, epoch_cap=100):
     (FM.py:261-262), −0.0075 without a cap in DFM (DFM.py:299-300) and −0.01
     without a cap in AFM (AFM.py:330-331)."""
     args = tr.args
-    t2 = time()
-    if args.Result == 0:
-        res = _evaluate(tr)
-        a1, a2, tk = res
-        _log(tr, "Dataset=%s %s Init: \t train=AUC:%.4f;test=AUC:%.4f,HR:%.4f,NDCG:%.4f,PRE:%.4f;"
-             "[%.1f s]" % (args.dataset, tr.method, a1, a2, tk[0], tk[1], tk[2], time() - t2))
+    _report_init(tr)
     tr.loss_epoch = []
     for epoch in range(1, tr.epoch):
         loss = 0.0
@@ -270,12 +268,7 @@ def run_training(tr, negatives=2, neg_label=0, plateau=-0.0075, epoch_cap=100):
 def run_training_hhfm(tr):
     """OurModel7.py:349-413."""
     args = tr.args
-    t2 = time()
-    if args.Result == 0:
-        res = _evaluate(tr)
-        a1, a2, tk = res
-        _log(tr, "Dataset=%s %s Init: \t train=AUC:%.4f;test=AUC:%.4f,HR:%.4f,NDCG:%.4f,PRE:%.4f;"
-             "[%.1f s]" % (args.dataset, tr.method, a1, a2, tk[0], tk[1], tk[2], time() - t2))
+    _report_init(tr)
     tr.loss_epoch = []
     td = tr.time_dimension
     for epoch in range(1, tr.epoch):

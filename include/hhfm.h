@@ -383,14 +383,15 @@ int hhfm_afm_catalog_topk_ex(const int32_t* qidx, int64_t B, int32_t F, const vo
  * H6 — one training step (`partial_fit`, sess.run((loss, optimizer))).
  *   FM   (FM.py:123-136):        loss = Σ (y − out)²/2 + λ·Σ E²/2
  *   HHFM (OurModel7.py:172-193): loss = −Σ log σ(pos − max_j neg_j) + λ·Σ E²/2
- * optimizer (TF-1.x semantics, FM.py:129-136; `acc` slots per variable):
- *   0 = AdagradOptimizer  accum += g², var -= lr·g·rsqrt(accum); n floats
- *       initialised to 0.1 (TF's initial_accumulator_value);
- *   1 = GradientDescentOptimizer (no slots);
- *   2 = MomentumOptimizer(momentum = 0.95)  accum = accum·0.95 + g,
+ * optimizer (enum hhfm_optimizer below; TF-1.x semantics, FM.py:129-136; `acc`
+ * slots per variable):
+ *   HHFM_OPT_ADAGRAD   AdagradOptimizer  accum += g², var -= lr·g·rsqrt(accum);
+ *       n floats initialised to 0.1 (TF's initial_accumulator_value);
+ *   HHFM_OPT_SGD       GradientDescentOptimizer (no slots);
+ *   HHFM_OPT_MOMENTUM  MomentumOptimizer(momentum = 0.95)  accum = accum·0.95 + g,
  *       var -= accum·lr; n floats initialised to 0;
- *   3 = AdamOptimizer(β1 0.9, β2 0.999, ε 1e-8)  2n floats (m, then v)
- *       initialised to 0; β1^t, β2^t and a started flag live in the
+ *   HHFM_OPT_ADAM      AdamOptimizer(β1 0.9, β2 0.999, ε 1e-8)  2n floats (m,
+ *       then v) initialised to 0; β1^t, β2^t and a started flag live in the
  *       workspace (zero-filled once = step 1; a power that underflows to 0
  *       stays 0, as TF's does).
  * Variables whose TF gradient is an IndexedSlices (an embedding_lookup with
@@ -399,14 +400,22 @@ int hhfm_afm_catalog_topk_ex(const int32_t* qidx, int64_t B, int32_t F, const vo
  * rules: Momentum updates only the rows the batch touched, Adam decays m
  * and v of every row (AdamOptimizer._apply_sparse_shared).
  * E, w are fp32 and updated in place; *loss (device float) receives the loss
- * of the pre-update parameters.  The workspace (hhfm_train_workspace bytes)
- * must be zero-filled once; the step leaves it zeroed except Adam's β powers.  HHFM: X [B][ncols]
- * full rows [user, item, ctx..., time...], Neg [B][NG] negative item ids,
- * NG <= 16.
+ * of the pre-update parameters.  The workspace (hhfm_train_workspace bytes:
+ * gradient buffers, 16 scalars, the touched-row mask; the layout is
+ * fm_train_plan's in train.hip) must be zero-filled once; the step leaves it
+ * zeroed except Adam's β powers.  HHFM: X [B][ncols] full rows [user, item,
+ * ctx..., time...], Neg [B][NG] negative item ids, NG <= 16.
  * B = 0 is a step like any other in all four train entry points (the l2
  * term still decays its variable, Adam's moments and powers still advance);
  * the row pointers (idx / X, y / Neg) may then be NULL.
  * ---------------------------------------------------------------------- */
+enum hhfm_optimizer {
+  HHFM_OPT_ADAGRAD = 0,
+  HHFM_OPT_SGD = 1,
+  HHFM_OPT_MOMENTUM = 2,
+  HHFM_OPT_ADAM = 3
+};
+
 size_t hhfm_train_workspace(int64_t features_M, int32_t k);
 int hhfm_fm_train_step(const int32_t* idx, const float* y, int64_t B, int32_t F, float* E,
                        float* w, float* w0, int64_t features_M, int32_t k, float lr,
@@ -424,14 +433,16 @@ int hhfm_hhfm_train_step(const int32_t* X, const int32_t* Neg, int64_t B, int32_
  * one step of the optimizer (codes as above) on every variable, in place.
  * W[l] is layer l row-major [d_{l-1}][d_l] (d_{-1} = F·k), bias[l] [d_l], Wp
  * the concat projection [F + k + d_{L-1}], bp a device float.  acc (every
- * optimizer but 1): 2L+4 device slot arrays in the order E, w, W_0..W_{L-1},
+ * optimizer but HHFM_OPT_SGD): 2L+4 device slot arrays in the order E, w, W_0..W_{L-1},
  * b_0..b_{L-1}, Wp, bp, sized and initialised as above.
  * The workspace (hhfm_dfm_train_workspace bytes for batches of at most B rows)
  * must be zero-filled once; the step keeps its gradient regions zeroed.  Its
  * persistent part (every gradient the step accumulates into, Adam's β
- * powers) leads at offsets independent of B, so a later smaller batch finds
- * it where the last step left it, and a workspace grown for a larger batch keeps the state when that
- * prefix (hhfm_dfm_train_state_bytes) is copied into the new zero-filled one.
+ * powers, the touched-row mask; the layout is TrainWs's in train.hip) leads at
+ * offsets independent of B, so a later smaller batch finds it where the last
+ * step left it, and a workspace grown for a larger batch keeps the state when
+ * that prefix (hhfm_dfm_train_state_bytes) is copied into the new zero-filled
+ * one.
  * Requires k % 4 == 0, L <= 4, F + k + d_{L-1} <= 1024. */
 int hhfm_dfm_train_workspace(int64_t B, int32_t F, int32_t k, int64_t features_M,
                              int32_t nlayers, const int32_t* layer_dims, size_t* ws_bytes);
@@ -452,7 +463,7 @@ int hhfm_dfm_train_step(const int32_t* idx, const float* y, int64_t B, int32_t F
  * one step of the optimizer (codes as above) on every variable, in place:
  * E [M][k], w [M], w0 (device float), W = attention_W [k][A] row-major,
  * b = attention_b [A], pvec = attention_p [A], P = prediction [k].  acc
- * (every optimizer but 1): 7 device slot arrays in the order E, w, w0, W, b,
+ * (every optimizer but HHFM_OPT_SGD): 7 device slot arrays in the order E, w, w0, W, b,
  * pvec, P, sized and initialised as above.  The workspace
  * (hhfm_afm_train_workspace bytes for batches of at most B rows) must be
  * zero-filled once; the step keeps its gradient regions zeroed; grown as for

@@ -250,3 +250,206 @@ def test_dfm_projection_auto_plan():
     # outside the fused envelope (k % 16 != 0) nothing is planned
     assert (nat.dfm_forward_workspace_ex(1 << 20, 5, 40, 5051, dims, 1, 1)
             == nat.dfm_forward_workspace_ex(1 << 20, 5, 40, 5051, dims, 1, 0))
+
+
+# ---------------------------------------------------------------------------
+# H6 train entry points: argument checks and workspace sizes.  Every call
+# below returns before the first launch (a check fails, or the workspace is one
+# byte short), so none of it needs a device.
+# ---------------------------------------------------------------------------
+_vp, _i32, _i64, _f32, _sz = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float,
+                              ctypes.c_size_t)
+_D = 0x1000            # a non-null pointer that is never dereferenced
+EINVAL, EUNSUPPORTED, EWORKSPACE = -1, -2, -3
+ADAGRAD, SGD, MOMENTUM, ADAM = 0, 1, 2, 3
+_DFM_DIMS = [24, 40]
+
+
+def _ptrs(vals):
+    return (_vp * len(vals))(*vals)
+
+
+# model -> (symbol, [(argument, ctype)] in ABI order, valid arguments but `ws_bytes`)
+_TRAIN = {
+    "fm": ("hhfm_fm_train_step",
+           [("idx", _vp), ("y", _vp), ("B", _i64), ("F", _i32), ("E", _vp), ("w", _vp),
+            ("w0", _vp), ("M", _i64), ("k", _i32), ("lr", _f32), ("lam", _f32), ("opt", _i32),
+            ("accE", _vp), ("accw", _vp), ("accw0", _vp), ("ws", _vp), ("ws_bytes", _sz),
+            ("loss", _vp), ("stream", _vp)],
+           dict(idx=_D, y=_D, B=7, F=5, E=_D, w=_D, w0=_D, M=40, k=8, lr=0.1, lam=0.1,
+                opt=ADAGRAD, accE=_D, accw=_D, accw0=_D, ws=_D, loss=_D, stream=None)),
+    "hhfm": ("hhfm_hhfm_train_step",
+             [("X", _vp), ("Neg", _vp), ("B", _i64), ("ncols", _i32), ("c0", _i32), ("c1", _i32),
+              ("t0", _i32), ("t1", _i32), ("NG", _i32), ("E", _vp), ("M", _i64), ("k", _i32),
+              ("lr", _f32), ("lam", _f32), ("opt", _i32), ("accE", _vp), ("ws", _vp),
+              ("ws_bytes", _sz), ("loss", _vp), ("stream", _vp)],
+             dict(X=_D, Neg=_D, B=7, ncols=5, c0=2, c1=4, t0=4, t1=5, NG=10, E=_D, M=40, k=8,
+                  lr=0.1, lam=0.1, opt=ADAGRAD, accE=_D, ws=_D, loss=_D, stream=None)),
+    "dfm": ("hhfm_dfm_train_step",
+            [("idx", _vp), ("y", _vp), ("B", _i64), ("F", _i32), ("E", _vp), ("w", _vp),
+             ("M", _i64), ("k", _i32), ("L", _i32), ("dims", _vp), ("W", _vp), ("bias", _vp),
+             ("Wp", _vp), ("bp", _vp), ("lr", _f32), ("lam", _f32), ("opt", _i32), ("acc", _vp),
+             ("ws", _vp), ("ws_bytes", _sz), ("loss", _vp), ("stream", _vp)],
+            dict(idx=_D, y=_D, B=7, F=5, E=_D, w=_D, M=40, k=8, L=len(_DFM_DIMS),
+                 dims=(_i32 * len(_DFM_DIMS))(*_DFM_DIMS), W=_ptrs([_D] * len(_DFM_DIMS)),
+                 bias=_ptrs([_D] * len(_DFM_DIMS)), Wp=_D, bp=_D, lr=0.1, lam=0.1, opt=ADAGRAD,
+                 acc=_ptrs([_D] * (2 * len(_DFM_DIMS) + 4)), ws=_D, loss=_D, stream=None)),
+    "afm": ("hhfm_afm_train_step",
+            [("idx", _vp), ("y", _vp), ("B", _i64), ("F", _i32), ("E", _vp), ("w", _vp),
+             ("w0", _vp), ("M", _i64), ("k", _i32), ("A", _i32), ("W", _vp), ("b", _vp),
+             ("pvec", _vp), ("P", _vp), ("lr", _f32), ("lam", _f32), ("opt", _i32), ("acc", _vp),
+             ("ws", _vp), ("ws_bytes", _sz), ("loss", _vp), ("stream", _vp)],
+            dict(idx=_D, y=_D, B=7, F=5, E=_D, w=_D, w0=_D, M=40, k=8, A=12, W=_D, b=_D, pvec=_D,
+                 P=_D, lr=0.1, lam=0.1, opt=ADAGRAD, acc=_ptrs([_D] * 7), ws=_D, loss=_D,
+                 stream=None)),
+}
+_ROWS = {"fm": ("idx", "y"), "hhfm": ("X", "Neg"), "dfm": ("idx", "y"), "afm": ("idx", "y")}
+_PARAMS = {"fm": ("E", "w", "w0", "loss", "ws"), "hhfm": ("E", "loss", "ws"),
+           "dfm": ("E", "w", "W", "bias", "Wp", "bp", "loss", "ws"),
+           "afm": ("E", "w", "w0", "W", "b", "pvec", "P", "loss", "ws")}
+_BAD_SHAPES = {"fm": (dict(B=-1), dict(F=0), dict(M=0)),
+               "hhfm": (dict(B=-1), dict(M=0), dict(ncols=1), dict(NG=0)),
+               "dfm": (dict(B=-1), dict(F=0), dict(M=0)),
+               "afm": (dict(B=-1), dict(F=0), dict(M=0))}
+_NSLOTS = {"dfm": 2 * len(_DFM_DIMS) + 4, "afm": 7}
+
+
+def _train_lib():
+    lib = ctypes.CDLL(LIB)
+    lib.hhfm_train_workspace.restype = _sz
+    lib.hhfm_train_workspace.argtypes = [_i64, _i32]
+    lib.hhfm_dfm_train_workspace.argtypes = [_i64, _i32, _i32, _i64, _i32, _vp,
+                                             ctypes.POINTER(_sz)]
+    lib.hhfm_dfm_train_state_bytes.argtypes = [_i32, _i32, _i64, _i32, _vp, ctypes.POINTER(_sz)]
+    lib.hhfm_afm_train_workspace.argtypes = [_i64, _i32, _i32, _i32, _i64, ctypes.POINTER(_sz)]
+    lib.hhfm_afm_train_state_bytes.argtypes = [_i32, _i32, _i32, _i64, ctypes.POINTER(_sz)]
+    for sym, sig, _ in _TRAIN.values():
+        getattr(lib, sym).argtypes = [t for _, t in sig]
+    return lib
+
+
+def _dfm_ws(lib, B, F, k, M, dims):
+    n = _sz(0)
+    assert lib.hhfm_dfm_train_workspace(B, F, k, M, len(dims), (_i32 * len(dims))(*dims),
+                                        ctypes.byref(n)) == 0
+    return n.value
+
+
+def _dfm_state(lib, F, k, M, dims):
+    n = _sz(0)
+    assert lib.hhfm_dfm_train_state_bytes(F, k, M, len(dims), (_i32 * len(dims))(*dims),
+                                          ctypes.byref(n)) == 0
+    return n.value
+
+
+def _afm_ws(lib, B, F, k, A, M):
+    n = _sz(0)
+    assert lib.hhfm_afm_train_workspace(B, F, k, A, M, ctypes.byref(n)) == 0
+    return n.value
+
+
+def _afm_state(lib, F, k, A, M):
+    n = _sz(0)
+    assert lib.hhfm_afm_train_state_bytes(F, k, A, M, ctypes.byref(n)) == 0
+    return n.value
+
+
+def _need(lib, model, a):
+    """The workspace bytes the step asks for with arguments ``a``."""
+    if model in ("fm", "hhfm"):
+        return lib.hhfm_train_workspace(a["M"], a["k"])
+    if model == "dfm":
+        return _dfm_ws(lib, a["B"], a["F"], a["k"], a["M"], _DFM_DIMS)
+    return _afm_ws(lib, a["B"], a["F"], a["k"], a["A"], a["M"])
+
+
+def _step(lib, model, short=1, **over):
+    """The step's return code with the valid arguments, ``over`` applied and a
+    workspace ``short`` bytes smaller than needed: every check passes iff the
+    code is HHFM_EWORKSPACE, and nothing is ever launched."""
+    sym, sig, base = _TRAIN[model]
+    a = dict(base, **over)
+    shape_ok = not any(all(a[n] == v for n, v in bad.items()) for bad in _BAD_SHAPES[model])
+    a["ws_bytes"] = _need(lib, model, a) - short if shape_ok else 1 << 40
+    return getattr(lib, sym)(*[a[n] for n, _ in sig])
+
+
+@pytest.mark.parametrize("model", ["fm", "hhfm", "dfm", "afm"])
+def test_train_step_return_code_precedence(model):
+    """The order of the step's checks: shape (HHFM_EINVAL), NG and the
+    optimizer code (HHFM_EUNSUPPORTED), parameter, row and slot pointers
+    (HHFM_EINVAL), then the workspace size (HHFM_EWORKSPACE)."""
+    lib = _train_lib()
+    # all valid but a workspace one byte short; an empty batch needs no rows
+    assert _step(lib, model) == EWORKSPACE
+    assert _step(lib, model, **{n: None for n in _ROWS[model]}, B=0) == EWORKSPACE
+    for opt in (ADAGRAD, SGD, MOMENTUM, ADAM):
+        assert _step(lib, model, opt=opt) == EWORKSPACE
+    for bad in _BAD_SHAPES[model]:
+        assert _step(lib, model, **bad) == EINVAL, bad
+        assert _step(lib, model, opt=4, **bad) == EINVAL, bad      # the shape is checked first
+    if model == "hhfm":
+        assert _step(lib, model, NG=16) == EWORKSPACE
+        assert _step(lib, model, NG=17) == EUNSUPPORTED
+        assert _step(lib, model, NG=17, E=None) == EUNSUPPORTED
+    for opt in (4, -1):
+        assert _step(lib, model, opt=opt) == EUNSUPPORTED
+        for n in _PARAMS[model] + _ROWS[model]:                    # the optimizer, then pointers
+            assert _step(lib, model, opt=opt, **{n: None}) == EUNSUPPORTED, n
+    for n in _PARAMS[model]:
+        assert _step(lib, model, **{n: None}) == EINVAL, n
+    for n in _ROWS[model]:
+        assert _step(lib, model, **{n: None}) == EINVAL, n
+    # slot arrays: needed by every optimizer but SGD
+    if model in ("fm", "hhfm"):
+        for n in ("accE", "accw", "accw0") if model == "fm" else ("accE",):
+            for opt in (ADAGRAD, MOMENTUM, ADAM):
+                assert _step(lib, model, opt=opt, **{n: None}) == EINVAL, (n, opt)
+            assert _step(lib, model, opt=SGD, **{n: None}) == EWORKSPACE, n
+    else:
+        ns = _NSLOTS[model]
+        for opt in (ADAGRAD, MOMENTUM, ADAM):
+            assert _step(lib, model, opt=opt, acc=None) == EINVAL
+            for hole in (0, ns - 1):
+                acc = _ptrs([None if i == hole else _D for i in range(ns)])
+                assert _step(lib, model, opt=opt, acc=acc) == EINVAL, (opt, hole)
+        assert _step(lib, model, opt=SGD, acc=None) == EWORKSPACE
+    if model == "dfm":
+        for n in ("W", "bias"):
+            for hole in (0, len(_DFM_DIMS) - 1):
+                arr = _ptrs([None if i == hole else _D for i in range(len(_DFM_DIMS))])
+                assert _step(lib, model, **{n: arr}) == EINVAL, (n, hole)
+
+
+def test_train_workspace_sizes():
+    """The train workspaces' byte sizes, as the library this refactor started
+    from reports them (the literals below were recorded from that build)."""
+    lib = _train_lib()
+    for M, k in [(1, 1), (40, 8), (256, 4), (257, 128)]:
+        assert lib.hhfm_train_workspace(M, k) == 4 * M * k + 4 * M + 64 + (M + 255) // 256 * 256
+
+    def r64(n):   # every region of a plan workspace is rounded up to 64 floats
+        return (n + 63) // 64 * 64
+
+    # DeepFM: (B, F, k, M, dims) -> (workspace, state) bytes
+    dfm = {(0, 5, 8, 100, (16,)): (16896, 4608), (13, 3, 4, 257, (24, 40, 24, 8)): (62976, 6656),
+           (301, 5, 16, 267, (24, 40)): (513024, 19456)}
+    for (B, F, k, M, dims), (ws, state) in dfm.items():
+        assert _dfm_ws(lib, B, F, k, M, list(dims)) == ws
+        assert _dfm_state(lib, F, k, M, list(dims)) == state
+        # the state prefix is scal | dE | dw | dWp | touched, whatever B is
+        assert state == 4 * (r64(16) + r64(M * k) + r64(M) + r64(F + k + dims[-1])
+                             + r64((M + 3) // 4))
+        sizes = [_dfm_ws(lib, b, F, k, M, list(dims)) for b in (0, 1, 8, 9, 1000)]
+        assert sizes == sorted(sizes) and sizes[0] > state and sizes[1] == sizes[2] < sizes[3]
+    # AFM: (B, F, k, A, M) -> (workspace, state) bytes
+    afm = {(0, 2, 4, 4, 10): (2816, 2048), (13, 16, 8, 12, 257): (345344, 11776),
+           (301, 5, 16, 32, 267): (1592320, 22016)}
+    for (B, F, k, A, M), (ws, state) in afm.items():
+        assert _afm_ws(lib, B, F, k, A, M) == ws
+        assert _afm_state(lib, F, k, A, M) == state
+        # scal | dE | dw | dW | db | dp | dP | touched, whatever B is
+        assert state == 4 * (r64(16) + r64(M * k) + r64(M) + r64(k * A) + 2 * r64(A) + r64(k)
+                             + r64((M + 3) // 4))
+        sizes = [_afm_ws(lib, b, F, k, A, M) for b in (0, 1, 9, 1000)]
+        assert sizes == sorted(sizes) and sizes[0] > state

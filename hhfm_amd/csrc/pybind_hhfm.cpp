@@ -404,6 +404,32 @@ PYBIND11_MODULE(_hhfm, m) {
           check(rc, "hhfm_fm_train_step");
         });
 
+  m.def("fm_train_step_ex",
+        [](uptr idx, uptr y, int64_t B, int F, uptr E, uptr w, uptr w0, int64_t M, int k,
+           float lr, float lam, int opt, float keep, uint64_t seed, uptr accE, uptr accw,
+           uptr accw0, uptr ws, size_t ws_bytes, uptr loss, uptr stream) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_fm_train_step_ex(P<const int32_t>(idx), P<const float>(y), B, F,
+                                       P<float>(E), P<float>(w), P<float>(w0), M, k, lr, lam,
+                                       opt, keep, seed, P<float>(accE), P<float>(accw),
+                                       P<float>(accw0), P<void>(ws), ws_bytes, P<float>(loss),
+                                       P<void>(stream));
+          }
+          check(rc, "hhfm_fm_train_step_ex");
+        });
+
+  m.def("dropout_mask", [](uint64_t seed, int site, int64_t rows, int n, float keep, uptr binary,
+                           uptr stream) {
+    int rc;
+    {
+      py::gil_scoped_release nogil;
+      rc = hhfm_dropout_mask(seed, site, rows, n, keep, P<float>(binary), P<void>(stream));
+    }
+    check(rc, "hhfm_dropout_mask");
+  });
+
   m.def("hhfm_train_step",
         [](uptr X, uptr Neg, int64_t B, int ncols, int c0, int c1, int t0, int t1, int NG,
            uptr E, int64_t M, int k, float lr, float lam, int opt, uptr accE, uptr ws,
@@ -491,6 +517,28 @@ PYBIND11_MODULE(_hhfm, m) {
                                      P<float>(loss), P<void>(stream));
           }
           check(rc, "hhfm_afm_train_step");
+        });
+
+  m.def("afm_train_step_ex",
+        [](uptr idx, uptr y, int64_t B, int F, uptr E, uptr w, uptr w0, int64_t M, int k, int A,
+           uptr W, uptr b, uptr pvec, uptr Pv, float lr, float lam, int opt, float keep_att,
+           float keep_afm, uint64_t seed, std::vector<uptr> acc, uptr ws, size_t ws_bytes,
+           uptr loss, uptr stream) {
+          if (opt != HHFM_OPT_SGD && acc.size() != 7)
+            throw py::value_error("acc needs 7 slot arrays (E, w, w0, W, b, pvec, P)");
+          std::vector<float*> av(acc.size());
+          for (size_t i = 0; i < acc.size(); ++i) av[i] = P<float>(acc[i]);
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_afm_train_step_ex(P<const int32_t>(idx), P<const float>(y), B, F,
+                                        P<float>(E), P<float>(w), P<float>(w0), M, k, A,
+                                        P<float>(W), P<float>(b), P<float>(pvec), P<float>(Pv),
+                                        lr, lam, opt, keep_att, keep_afm, seed,
+                                        av.empty() ? nullptr : av.data(), P<void>(ws), ws_bytes,
+                                        P<float>(loss), P<void>(stream));
+          }
+          check(rc, "hhfm_afm_train_step_ex");
         });
 
   m.def("topk_dense",

@@ -8,6 +8,9 @@
 //                         (Newcode/DFM.py:139-155, 214-217)
 //   hhfm_afm_train_step   replaces the same for AFM
 //                         (Newcode/AFM.py:144-156, 205-207)
+//   hhfm_fm_train_step_ex / hhfm_afm_train_step_ex  the same with `--keep` < 1
+//                         (tf.nn.dropout, FM.py:114, AFM.py:126 / :134) on the
+//                         mask of dropout.h; hhfm_dropout_mask writes that mask
 //
 // One wave per batch row computes the forward score(s) and scatters the
 // gradient of the row's loss into dense fp32 gradient buffers with float
@@ -31,6 +34,7 @@
 #include <initializer_list>
 #include <iterator>
 
+#include "dropout.h"
 #include "gemm_mfma.h"
 
 namespace hhfm {
@@ -41,23 +45,44 @@ constexpr int kMaxNeg = 16;   // negatives per row (the reference samples 10, Ou
 // and a flag that is != 0 once Adam has taken a step (a separate flag: β1^t
 // underflows to exactly 0 after 828 steps (TF's flush-to-zero), and TF then
 // keeps using 0, so 0 cannot also mean "not started").  finish_loss zeroes
-// floats 0..3 (3 is unused).
+// floats 0..3 (3 is unused) and the double of kScalLoss64.
 constexpr int kScalBiasGrad = 0;   // Σ dL/d(out): the gradient of w0 / bp
 constexpr int kScalDataLoss = 1;   // the batch's loss without the l2 term
 constexpr int kScalSumSq = 2;      // Σ var² (pre-update) of the l2-regularised variables
+constexpr int kScalLoss64 = 4;     // floats 4..6 hold one 8-byte-aligned double (scal_loss64)
 constexpr int kScalAdam = 8;       // [β1^t, β2^t, started]
 constexpr int kScalFloats = 16;
 
+// The data loss of FM's dropout step, summed in double.  One wave per row adds
+// its r²/2 into one scalar: 32,773 float atomics leave the sum ~6e-6 (rms) off
+// in relative terms — the loss is then checked to 1e-5 — because every add
+// rounds to the running sum's ulp; with the dropped forward's larger
+// residuals that showed (measured up to 1.1e-5).  A double takes the same adds
+// exactly enough.  It lives in the scalar block's unused floats, at whichever
+// of floats 4 / 5 is 8-byte aligned (the block itself is only 4-byte aligned
+// in fm_train_plan), is 0 between steps like the rest, and finish_loss adds
+// it to the float slot (0 in every step that does not use it).
+__host__ __device__ inline double* scal_loss64(float* scal) {
+  return reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(scal + kScalLoss64) + 7) &
+                                   ~uintptr_t(7));
+}
+
+// DROP: tf.nn.dropout on the k-vector FM_OUT (FM.py:114; dropout.h, site 0, the
+// row index the batch row b): column c enters out as t_c / keep · bin_c and
+// its gradient carries the same factor; a dropped column scatters nothing.
+template <bool DROP>
 __global__ __launch_bounds__(256) void fm_train_rows(
     const int32_t* __restrict__ idx, const float* __restrict__ y, int64_t B, int F,
     const float* __restrict__ E, const float* __restrict__ w, const float* __restrict__ w0,
-    int64_t M, int k, float* __restrict__ dE, float* __restrict__ dw, float* __restrict__ scal) {
+    int64_t M, int k, float* __restrict__ dE, float* __restrict__ dw, float* __restrict__ scal,
+    DropoutArgs dr) {
   const int l = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
   const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
   for (int64_t b = wave; b < B; b += nwave) {
     const int32_t* x = idx + b * F;
     float t = 0.f;
+    [[maybe_unused]] LaneDropout ld;
     for (int c = l; c < k; c += kWave) {
       float s = 0.f, q = 0.f;
       for (int f = 0; f < F; ++f) {
@@ -65,7 +90,10 @@ __global__ __launch_bounds__(256) void fm_train_rows(
         s += v;
         q += v * v;
       }
-      t += 0.5f * (s * s - q);
+      if constexpr (DROP)
+        t += 0.5f * (s * s - q) / dr.keep0 * ld.binary(dr, dr.keep0, kDropSiteFm, b, c);
+      else
+        t += 0.5f * (s * s - q);
     }
     t = group_sum<kWave>(t);
     float fb = 0.f;
@@ -74,17 +102,26 @@ __global__ __launch_bounds__(256) void fm_train_rows(
     const float r = y[b] - out;        // l2_loss(y - out) = r²/2   FM.py:124
     const float g = -r;                // d/d out
     for (int c = l; c < k; c += kWave) {
+      float gc = g;
+      if constexpr (DROP) {
+        const float bin = ld.binary(dr, dr.keep0, kDropSiteFm, b, c);
+        if (bin == 0.f) continue;
+        gc = g * bin / dr.keep0;
+      }
       float s = 0.f;
       for (int f = 0; f < F; ++f) s += E[(int64_t)clamp_id(x[f], M) * k + c];
       for (int f = 0; f < F; ++f) {
         const int64_t id = clamp_id(x[f], M);
-        atomicAdd(dE + id * k + c, g * (s - E[id * k + c]));   // ∂out/∂e_f = Σe − e_f
+        atomicAdd(dE + id * k + c, gc * (s - E[id * k + c]));   // ∂out/∂e_f = Σe − e_f
       }
     }
     for (int f = l; f < F; f += kWave) atomicAdd(dw + clamp_id(x[f], M), g);
     if (l == 0) {
       atomicAdd(scal + kScalBiasGrad, g);
-      atomicAdd(scal + kScalDataLoss, 0.5f * r * r);
+      if constexpr (DROP)
+        atomicAdd(scal_loss64(scal), 0.5 * ((double)r * (double)r));
+      else
+        atomicAdd(scal + kScalDataLoss, 0.5f * r * r);
     }
   }
 }
@@ -263,8 +300,11 @@ __global__ __launch_bounds__(256) void mark_rows(const int32_t* __restrict__ idx
 }
 
 __global__ void finish_loss(float* scal, float lam, float* loss) {
-  loss[0] = scal[kScalDataLoss] + lam * 0.5f * scal[kScalSumSq];   // + l2_regularizer(λ)(var)
+  double* l64 = scal_loss64(scal);
+  const float data = (float)((double)scal[kScalDataLoss] + *l64);
+  loss[0] = data + lam * 0.5f * scal[kScalSumSq];   // + l2_regularizer(λ)(var)
   scal[0] = scal[1] = scal[2] = scal[3] = 0.f;
+  *l64 = 0.0;
 }
 
 static int grid_for_n(int64_t n) {
@@ -642,6 +682,15 @@ constexpr int kAfmTrainMaxNp = kAfmTrainMaxF * (kAfmTrainMaxF - 1) / 2;
 constexpr int kAfmTrainMaxKA = 256;                        // k, A <= 256
 constexpr int kAfmSplitK = 512;                            // combos per dW split
 
+// DROP: tf.nn.dropout on the softmaxed attention (AFM.py:126; dropout.h site 1,
+// keep0) and on the k-vector AFM (AFM.py:134; site 2, keep1), row index m.
+// With m1_p = bin1_p / keep0, m2_c = bin2_c / keep1 and ã = a ⊙ m1:
+//   out  = Σ_c m2_c P_c Σ_p ã_p pr_pc + Σw + w0      s_p = Σ_c P_c m2_c pr_pc
+//   da_p = m1_p·g·s_p, dlogit = a ⊙ (da − Σ a·da) on the undropped softmax a
+//   dP_c = g·m2_c·Σ_p ã_p pr_pc
+// `att` receives ã for the scatter.  k <= 256 and np <= 120: one Philox block
+// per lane and site serves the lane's columns l + 64·kc and pairs l + 64·j.
+template <bool DROP>
 __global__ __launch_bounds__(256) void afm_train_head(
     const int32_t* __restrict__ idx, const float* __restrict__ y, int64_t B, int F,
     const float* __restrict__ E, const float* __restrict__ w, const float* __restrict__ w0,
@@ -649,7 +698,7 @@ __global__ __launch_bounds__(256) void afm_train_head(
     const float* __restrict__ P, float* __restrict__ Gz, float* __restrict__ PT,
     float* __restrict__ GzT, int64_t Kp, float* __restrict__ att, float* __restrict__ gvec,
     float* __restrict__ dP, float* __restrict__ dpv, float* __restrict__ db,
-    float* __restrict__ dw, float* __restrict__ scal) {
+    float* __restrict__ dw, float* __restrict__ scal, DropoutArgs dr) {
   constexpr int NC = kAfmTrainMaxKA / kWave;
   __shared__ float sp_all[4][kAfmTrainMaxNp], lg_all[4][kAfmTrainMaxNp];
   const int l = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -665,6 +714,16 @@ __global__ __launch_bounds__(256) void afm_train_head(
   for (int64_t m = wave; m < B; m += nwave) {
     const int32_t* x = idx + m * F;
     const int64_t c0 = m * np;   // first combo of this row
+    // this lane's m2 of columns l + 64·kc and m1 of pairs l, l + 64
+    [[maybe_unused]] float m2[NC], m1a = 1.f, m1b = 1.f;
+    if constexpr (DROP) {
+      const Philox4 b2 = dropout_block(dr.key0, dr.key1, kDropSiteAfmVec, m, l);
+#pragma unroll
+      for (int kc = 0; kc < NC; ++kc) m2[kc] = dropout_binary(dr.keep1, b2.v[kc]) / dr.keep1;
+      const Philox4 b1 = dropout_block(dr.key0, dr.key1, kDropSiteAfmAtt, m, l);
+      m1a = dropout_binary(dr.keep0, b1.v[0]) / dr.keep0;
+      m1b = dropout_binary(dr.keep0, b1.v[1]) / dr.keep0;
+    }
     // s_p = P·(e_i ⊙ e_j)   (lanes over k; one wave sum per pair and chunk)
     for (int p = l; p < np; p += kWave) sp[p] = 0.f;
 #pragma unroll
@@ -675,7 +734,8 @@ __global__ __launch_bounds__(256) void afm_train_head(
 #pragma unroll
       for (int f = 0; f < kAfmTrainMaxF; ++f)
         ev[f] = (f < F && c < k) ? E[(int64_t)clamp_id(x[f], M) * k + c] : 0.f;
-      const float pc = c < k ? P[c] : 0.f;
+      float pc = c < k ? P[c] : 0.f;
+      if constexpr (DROP) pc *= m2[kc];
       int p = 0;
 #pragma unroll
       for (int i = 0; i < kAfmTrainMaxF; ++i)
@@ -705,7 +765,12 @@ __global__ __launch_bounds__(256) void afm_train_head(
     for (int p = l; p < np; p += kWave) se += expf(lg[p] - mx);
     se = group_sum<kWave>(se);
     float os = 0.f;
-    for (int p = l; p < np; p += kWave) os += expf(lg[p] - mx) / se * sp[p];
+    for (int p = l; p < np; p += kWave) {
+      if constexpr (DROP)
+        os += expf(lg[p] - mx) / se * (p < kWave ? m1a : m1b) * sp[p];
+      else
+        os += expf(lg[p] - mx) / se * sp[p];
+    }
     os = group_sum<kWave>(os);
     float fb = 0.f;
     for (int f = l; f < F; f += kWave) fb += w[clamp_id(x[f], M)];
@@ -716,13 +781,25 @@ __global__ __launch_bounds__(256) void afm_train_head(
     sl += 0.5f * g * g;
     // da_p = g·s_p, dlogit_p = a_p (da_p − Σ a·da)
     float t = 0.f;
-    for (int p = l; p < np; p += kWave) t += expf(lg[p] - mx) / se * (g * sp[p]);
+    for (int p = l; p < np; p += kWave) {
+      if constexpr (DROP)
+        t += expf(lg[p] - mx) / se * ((p < kWave ? m1a : m1b) * (g * sp[p]));
+      else
+        t += expf(lg[p] - mx) / se * (g * sp[p]);
+    }
     t = group_sum<kWave>(t);
     for (int p = l; p < np; p += kWave) {
       const float a = expf(lg[p] - mx) / se;
-      att[c0 + p] = a;
-      lg[p] = a * (g * sp[p] - t);                   // lg now holds dlogit
-      sp[p] = a;                                     // sp now holds att
+      if constexpr (DROP) {
+        const float m1 = p < kWave ? m1a : m1b;
+        att[c0 + p] = a * m1;                        // ã for the scatter
+        lg[p] = a * (m1 * (g * sp[p]) - t);
+        sp[p] = a * m1;
+      } else {
+        att[c0 + p] = a;
+        lg[p] = a * (g * sp[p] - t);                 // lg now holds dlogit
+        sp[p] = a;                                   // sp now holds att
+      }
     }
     if (l == 0) gvec[m] = g;
     __builtin_amdgcn_wave_barrier();
@@ -766,7 +843,10 @@ __global__ __launch_bounds__(256) void afm_train_head(
               PT[c * Kp + c0 + p] = pr;
               ++p;
             }
-        accP[kc] = fmaf(g, afm, accP[kc]);
+        if constexpr (DROP)
+          accP[kc] = fmaf(g * m2[kc], afm, accP[kc]);
+        else
+          accP[kc] = fmaf(g, afm, accP[kc]);
       }
     }
     for (int f = l; f < F; f += kWave) atomicAdd(&dw[clamp_id(x[f], M)], g);
@@ -786,10 +866,14 @@ __global__ __launch_bounds__(256) void afm_train_head(
 }
 
 // dE[x_f][c] += Σ_{pairs ∋ f} (DP + a_p·d·P_c) ⊙ e_other   (wave per row, lanes over k)
+// DROP: `att` holds ã and the AFM-path term is ã_p·d·P_c·m2_c, m2 regenerated
+// from the counter (site 2); the DP term is unchanged.
+template <bool DROP>
 __global__ __launch_bounds__(256) void afm_train_scatter(
     const int32_t* __restrict__ idx, int64_t B, int F, const float* __restrict__ E, int64_t M,
     int k, const float* __restrict__ DP, const float* __restrict__ att,
-    const float* __restrict__ gvec, const float* __restrict__ P, float* __restrict__ dE) {
+    const float* __restrict__ gvec, const float* __restrict__ P, float* __restrict__ dE,
+    DropoutArgs dr) {
   const int l = threadIdx.x & 63;
   const int np = F * (F - 1) / 2;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
@@ -798,6 +882,7 @@ __global__ __launch_bounds__(256) void afm_train_scatter(
     const int32_t* x = idx + m * F;
     const int64_t c0 = m * np;
     const float g = gvec[m];
+    [[maybe_unused]] LaneDropout ld;
     for (int c = l; c < k; c += kWave) {
       float ev[kAfmTrainMaxF], de[kAfmTrainMaxF];
 #pragma unroll
@@ -805,7 +890,8 @@ __global__ __launch_bounds__(256) void afm_train_scatter(
         ev[f] = f < F ? E[(int64_t)clamp_id(x[f], M) * k + c] : 0.f;
         de[f] = 0.f;
       }
-      const float gp = g * P[c];
+      float gp = g * P[c];
+      if constexpr (DROP) gp *= ld.binary(dr, dr.keep1, kDropSiteAfmVec, m, c) / dr.keep1;
       int p = 0;
 #pragma unroll
       for (int i = 0; i < kAfmTrainMaxF; ++i)
@@ -903,6 +989,16 @@ static GemmArgs gemm_plain(int64_t M, int N, int64_t K, const void* A, int64_t l
   return g;
 }
 
+// binary[r][e] = the train kernels' dropout decision (dropout.h) as 0.f / 1.f
+__global__ __launch_bounds__(256) void dropout_mask(DropoutArgs dr, int site, int64_t rows, int n,
+                                                    float* __restrict__ binary) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / n;
+    binary[i] = dropout_element(dr.key0, dr.key1, site, r, (int)(i - r * n), dr.keep0);
+  }
+}
+
 }  // namespace hhfm
 
 using namespace hhfm;
@@ -911,12 +1007,33 @@ extern "C" size_t hhfm_train_workspace(int64_t features_M, int32_t k) {
   return fm_train_plan(features_M, k).bytes;
 }
 
+extern "C" int hhfm_dropout_mask(uint64_t seed, int32_t site, int64_t rows, int32_t n,
+                                 float keep, float* binary, void* stream) {
+  if (site < 0 || rows < 0 || n < 1 || !keep_ok(keep)) return HHFM_EINVAL;
+  if (rows == 0) return HHFM_OK;
+  if (!binary) return HHFM_EINVAL;
+  hipLaunchKernelGGL(dropout_mask, dim3(grid_for_n(rows * n)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), dropout_args(keep, keep, seed), site,
+                     rows, n, binary);
+  return (int)hipGetLastError();
+}
+
 extern "C" int hhfm_fm_train_step(const int32_t* idx, const float* y, int64_t B, int32_t F,
                                   float* E, float* w, float* w0, int64_t features_M, int32_t k,
                                   float lr, float lam, int32_t optimizer, float* accE,
                                   float* accw, float* accw0, void* workspace, size_t ws_bytes,
                                   float* loss, void* stream) {
-  if (B < 0 || F < 1 || k < 1 || features_M < 1) return HHFM_EINVAL;
+  return hhfm_fm_train_step_ex(idx, y, B, F, E, w, w0, features_M, k, lr, lam, optimizer, 1.f, 0,
+                               accE, accw, accw0, workspace, ws_bytes, loss, stream);
+}
+
+extern "C" int hhfm_fm_train_step_ex(const int32_t* idx, const float* y, int64_t B, int32_t F,
+                                     float* E, float* w, float* w0, int64_t features_M,
+                                     int32_t k, float lr, float lam, int32_t optimizer,
+                                     float keep, uint64_t seed, float* accE, float* accw,
+                                     float* accw0, void* workspace, size_t ws_bytes, float* loss,
+                                     void* stream) {
+  if (B < 0 || F < 1 || k < 1 || features_M < 1 || !keep_ok(keep)) return HHFM_EINVAL;
   if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
   if (!E || !w || !w0 || !loss || !workspace) return HHFM_EINVAL;
   if (B > 0 && (!idx || !y)) return HHFM_EINVAL;   // an empty batch reads no rows
@@ -927,9 +1044,12 @@ extern "C" int hhfm_fm_train_step(const int32_t* idx, const float* y, int64_t B,
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   float* ws = reinterpret_cast<float*>(workspace);
   float* scal = ws + p.off_scal;
-  if (B > 0)
-    hipLaunchKernelGGL(fm_train_rows, dim3(grid_for_n(B * 64)), dim3(256), 0, st, idx, y, B, F,
-                       E, w, w0, features_M, k, ws + p.off_dE, ws + p.off_dw, scal);
+  if (B > 0) {
+    auto rows = keep < 1.f ? fm_train_rows<true> : fm_train_rows<false>;
+    hipLaunchKernelGGL(rows, dim3(grid_for_n(B * 64)), dim3(256), 0, st, idx, y, B, F, E, w, w0,
+                       features_M, k, ws + p.off_dE, ws + p.off_dw, scal,
+                       dropout_args(keep, 1.f, seed));
+  }
   // sparse gradients (FM.py:123-126): w's always (embedding_lookup only), E's
   // when λ = 0 (no dense l2 term); w0 and the λ > 0 table are dense
   const OptVar vars[] = {
@@ -1126,8 +1246,23 @@ extern "C" int hhfm_afm_train_step(const int32_t* idx, const float* y, int64_t B
                                    float lr, float lambda_att, int32_t optimizer,
                                    float* const* acc, void* workspace, size_t ws_bytes,
                                    float* loss, void* stream) {
+  return hhfm_afm_train_step_ex(idx, y, B, F, E, w, w0, features_M, k, A, W, b, pvec, P, lr,
+                                lambda_att, optimizer, 1.f, 1.f, 0, acc, workspace, ws_bytes,
+                                loss, stream);
+}
+
+extern "C" int hhfm_afm_train_step_ex(const int32_t* idx, const float* y, int64_t B, int32_t F,
+                                      float* E, float* w, float* w0, int64_t features_M,
+                                      int32_t k, int32_t A, float* W, float* b, float* pvec,
+                                      float* P, float lr, float lambda_att, int32_t optimizer,
+                                      float keep_att, float keep_afm, uint64_t seed,
+                                      float* const* acc, void* workspace, size_t ws_bytes,
+                                      float* loss, void* stream) {
   AfmTrainPlan p;
-  if (!afm_train_plan(B, F, k, A, features_M, p)) return HHFM_EINVAL;
+  if (!afm_train_plan(B, F, k, A, features_M, p) || !keep_ok(keep_att) || !keep_ok(keep_afm))
+    return HHFM_EINVAL;
+  const bool drop = keep_att < 1.f || keep_afm < 1.f;
+  const DropoutArgs dr = dropout_args(keep_att, keep_afm, seed);
   if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
   if (!E || !w || !w0 || !W || !b || !pvec || !P || !loss || !workspace) return HHFM_EINVAL;
   if (B > 0 && (!idx || !y)) return HHFM_EINVAL;
@@ -1158,10 +1293,10 @@ extern "C" int hhfm_afm_train_step(const int32_t* idx, const float* y, int64_t B
     }
     // a few rows per wave: the per-wave dP / dp / db flush is k + 2A same-address atomics
     const unsigned hb = (unsigned)std::min<int64_t>(256, (B + 3) / 4);
-    hipLaunchKernelGGL(afm_train_head, dim3(hb), dim3(256), 0, st, idx, y,
-                       B, F, E, w, w0, features_M, k, A, at(p.off_R), pvec, P, at(p.off_Gz), PT,
-                       GzT, p.Kp, at(p.off_att), at(p.off_g), at(p.off_dP), at(p.off_dpv),
-                       at(p.off_db), at(p.off_dw), scal);
+    hipLaunchKernelGGL(drop ? afm_train_head<true> : afm_train_head<false>, dim3(hb), dim3(256),
+                       0, st, idx, y, B, F, E, w, w0, features_M, k, A, at(p.off_R), pvec, P,
+                       at(p.off_Gz), PT, GzT, p.Kp, at(p.off_att), at(p.off_g), at(p.off_dP),
+                       at(p.off_dpv), at(p.off_db), at(p.off_dw), scal, dr);
     if (p.Kp > p.n)
       hipLaunchKernelGGL(zero_cols, dim3(grid_for_n((int64_t)(k + A) * (p.Kp - p.n))),
                          dim3(256), 0, st, PT, k + A, p.Kp, p.n);
@@ -1175,9 +1310,9 @@ extern "C" int hhfm_afm_train_step(const int32_t* idx, const float* y, int64_t B
       hipLaunchKernelGGL(sum_splits, dim3(grid_for_n((int64_t)k * A)), dim3(256), 0, st,
                          (const float*)at(p.off_part), p.S, (int64_t)k * A, at(p.off_dW));
     }
-    hipLaunchKernelGGL(afm_train_scatter, dim3(grid_for_n(B * 64)), dim3(256), 0, st, idx, B, F,
-                       E, features_M, k, at(p.off_DP), at(p.off_att), at(p.off_g), P,
-                       at(p.off_dE));
+    hipLaunchKernelGGL(drop ? afm_train_scatter<true> : afm_train_scatter<false>,
+                       dim3(grid_for_n(B * 64)), dim3(256), 0, st, idx, B, F, E, features_M, k,
+                       at(p.off_DP), at(p.off_att), at(p.off_g), P, at(p.off_dE), dr);
   }
   // the table and w have IndexedSlices gradients (sparse); l2_regularizer(λ)
   // on attention_W only (AFM.py:146)

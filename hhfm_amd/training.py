@@ -64,6 +64,7 @@ def _state(model, names, opt, fixed_ws=False):
         st["opt"] = opt
         st["loss"] = torch.zeros(1, dtype=torch.float32, device=model.device)
         st["ws"], st["ws_rows"] = None, 0
+        st["step"] = 0   # partial_fit calls so far: the high word of the dropout seed
         if fixed_ws:
             M, k = model.weights["feature_embeddings"].shape
             st["ws"] = _grow(None, native().train_workspace(M, k), 0, model.device)
@@ -95,23 +96,43 @@ def _labels(model, data):
     return torch.as_tensor(np.asarray(data["Y"], np.float32).reshape(-1)).to(model.device)
 
 
+def _keep(value, n):
+    """``n`` dropout keep probabilities in (0, 1] (tf.nn.dropout raises
+    ValueError outside it)."""
+    keep = [float(x) for x in np.ravel(value)]
+    if len(keep) != n or not all(0.0 < x <= 1.0 for x in keep):
+        raise ValueError(f"keep must be {n} probabilit{'y' if n == 1 else 'ies'} in (0, 1], "
+                         f"got {value!r}")
+    return keep
+
+
+def _next_seed(model, st):
+    """The step's dropout seed (include/hhfm.h "Training dropout"): the model's
+    random_seed in the low word, the count of its earlier partial_fit calls in
+    the high word."""
+    seed = (int(model.random_seed) & 0xffffffff) | ((st["step"] & 0xffffffff) << 32)
+    st["step"] += 1
+    return seed
+
+
 def fm_partial_fit(model, data) -> float:
-    """FM.partial_fit (FM.py:168-171): one optimizer step, returns the loss."""
+    """FM.partial_fit (FM.py:168-171): one optimizer step, returns the loss
+    (of the dropped forward when keep < 1, FM.py:114)."""
     opt = _opt_code(model)
-    if model.keep != 1:
-        raise NotImplementedError("dropout keep < 1 is not implemented")
+    keep, = _keep(model.keep, 1)
     W = model.weights
     st = _state(model, ["feature_embeddings", "feature_bias", "bias"], opt, fixed_ws=True)
     X = model._idx(data["X"])
     y = _labels(model, data)
     B, F = X.shape
     M, k = W["feature_embeddings"].shape
-    native().fm_train_step(X.data_ptr(), y.data_ptr(), B, F, W["feature_embeddings"].data_ptr(),
-                           W["feature_bias"].data_ptr(), W["bias"].data_ptr(), M, k,
-                           float(model.learning_rate), float(model.lamda_bilinear), opt,
-                           st["feature_embeddings"].data_ptr(), st["feature_bias"].data_ptr(),
-                           st["bias"].data_ptr(), st["ws"].data_ptr(), st["ws"].numel(),
-                           st["loss"].data_ptr(), ops._stream(model.device))
+    native().fm_train_step_ex(X.data_ptr(), y.data_ptr(), B, F,
+                              W["feature_embeddings"].data_ptr(), W["feature_bias"].data_ptr(),
+                              W["bias"].data_ptr(), M, k, float(model.learning_rate),
+                              float(model.lamda_bilinear), opt, keep, _next_seed(model, st),
+                              st["feature_embeddings"].data_ptr(), st["feature_bias"].data_ptr(),
+                              st["bias"].data_ptr(), st["ws"].data_ptr(), st["ws"].numel(),
+                              st["loss"].data_ptr(), ops._stream(model.device))
     return float(st["loss"].item())
 
 
@@ -170,10 +191,10 @@ def dfm_partial_fit(model, data) -> float:
 
 def afm_partial_fit(model, data) -> float:
     """AFM.partial_fit (AFM.py:205-207): one TF step on every variable, loss
-    l2_loss(y − out) + l2_regularizer(λ)(attention_W) when λ > 0 (AFM.py:144-148)."""
+    l2_loss(y − out) + l2_regularizer(λ)(attention_W) when λ > 0 (AFM.py:144-148);
+    keep = [attention, AFM k-vector] (AFM.py:126, :134)."""
     opt = _opt_code(model)
-    if any(float(x) != 1.0 for x in np.ravel(model.keep)):
-        raise NotImplementedError("dropout keep < 1 is not implemented")
+    keep_att, keep_afm = _keep(model.keep, 2)
     W = model.weights
     names = ["feature_embeddings", "feature_bias", "bias", "attention_W", "attention_b",
              "attention_p", "prediction"]
@@ -188,13 +209,14 @@ def afm_partial_fit(model, data) -> float:
                     lambda: nat.afm_train_state_bytes(F, k, A, M))
     lam = float(model.lamda_attention) if model.lamda_attention > 0 else 0.0
     ptr = lambda n: W[n].data_ptr()  # noqa: E731
-    nat.afm_train_step(X.data_ptr(), y.data_ptr(), B, F, ptr("feature_embeddings"),
-                       ptr("feature_bias"), ptr("bias"), M, k, A, ptr("attention_W"),
-                       ptr("attention_b"), ptr("attention_p"), ptr("prediction"),
-                       float(model.learning_rate), lam, opt,
-                       [st[n].data_ptr() for n in names] if opt != _SGD else [],
-                       ws.data_ptr(), ws.numel(), st["loss"].data_ptr(),
-                       ops._stream(model.device))
+    nat.afm_train_step_ex(X.data_ptr(), y.data_ptr(), B, F, ptr("feature_embeddings"),
+                          ptr("feature_bias"), ptr("bias"), M, k, A, ptr("attention_W"),
+                          ptr("attention_b"), ptr("attention_p"), ptr("prediction"),
+                          float(model.learning_rate), lam, opt, keep_att, keep_afm,
+                          _next_seed(model, st),
+                          [st[n].data_ptr() for n in names] if opt != _SGD else [],
+                          ws.data_ptr(), ws.numel(), st["loss"].data_ptr(),
+                          ops._stream(model.device))
     return float(st["loss"].item())
 
 

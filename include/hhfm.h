@@ -428,6 +428,35 @@ int hhfm_hhfm_train_step(const int32_t* X, const int32_t* Neg, int64_t B, int32_
                          int32_t k, float lr, float lambda_l2, int32_t optimizer, float* accE,
                          void* workspace, size_t ws_bytes, float* loss, void* stream);
 
+/* Training dropout (`--keep` < 1 of FM.py:42-43, AFM.py:43-44).  The
+ * arithmetic and the gradient are tf.nn.dropout's (TF 1.x):
+ *   binary = floor(keep + uniform[0,1)),  y = x / keep · binary
+ * one mask per step, shared by its forward and backward pass; *loss is the
+ * loss of the dropped forward.  The mask is NOT TensorFlow's (its Philox
+ * stream is keyed by the graph seed and an op counter) but this library's,
+ * specified bit for bit: Philox4x32-10 keyed by the caller's 64-bit per-step
+ * `seed` (low word, high word); element e of row r at site s reads word
+ * (e >> 6) & 3 of the block with counter
+ *   ((e & 63) | ((e >> 8) << 6),  r & 0xffffffff,  r >> 32,  s)
+ * as u = float(x >> 9) · 2^-23 and binary = floorf(keep + u) in fp32.  Sites:
+ * 0 FM's k-vector FM_OUT (FM.py:114, n = k); 1 AFM's softmaxed attention
+ * (AFM.py:126, n = F(F−1)/2 pairs in i < j order); 2 AFM's k-vector
+ * (AFM.py:134, n = k).  r is the batch row.  (csrc/dropout.h; numpy
+ * restatement in tests/dropout_ref.py.)
+ * hhfm_fm_train_step_ex / hhfm_afm_train_step_ex are the steps above with
+ * that dropout; keep = 1 is exactly the plain step (hhfm_fm_train_step and
+ * hhfm_afm_train_step forward here with keep 1), and a keep that is NaN or
+ * outside (0, 1] is HHFM_EINVAL before anything is launched.  Workspaces are
+ * the plain steps'.  hhfm_dropout_mask writes the decisions themselves,
+ * binary [rows][n] floats 0 / 1 (rows = 0 is a no-op). */
+int hhfm_fm_train_step_ex(const int32_t* idx, const float* y, int64_t B, int32_t F, float* E,
+                          float* w, float* w0, int64_t features_M, int32_t k, float lr,
+                          float lambda_l2, int32_t optimizer, float keep, uint64_t seed,
+                          float* accE, float* accw, float* accw0, void* workspace,
+                          size_t ws_bytes, float* loss, void* stream);
+int hhfm_dropout_mask(uint64_t seed, int32_t site, int64_t rows, int32_t n, float keep,
+                      float* binary, void* stream);
+
 /* DeepFM (DFM.py:139-155, 214-217; use_fm = use_deep = True, loss "mse"):
  *   loss = Σ (y − out)²/2 + λ·(‖Wp‖² + Σ_l ‖W_l‖²)/2
  * one step of the optimizer (codes as above) on every variable, in place.
@@ -458,7 +487,9 @@ int hhfm_dfm_train_step(const int32_t* idx, const float* y, int64_t B, int32_t F
                         float* const* acc, void* workspace, size_t ws_bytes, float* loss,
                         void* stream);
 
-/* AFM (AFM.py:103-156, 205-207; attention = 1, keep = [1, 1]):
+/* AFM (AFM.py:103-156, 205-207; attention = 1; keep = [1, 1], or
+ * [keep_att, keep_afm] through hhfm_afm_train_step_ex — "Training dropout"
+ * above: keep_att on the softmaxed attention, keep_afm on the k-vector):
  *   loss = Σ (y − out)²/2 + λ·‖attention_W‖²/2
  * one step of the optimizer (codes as above) on every variable, in place:
  * E [M][k], w [M], w0 (device float), W = attention_W [k][A] row-major,
@@ -479,6 +510,12 @@ int hhfm_afm_train_step(const int32_t* idx, const float* y, int64_t B, int32_t F
                         float* W, float* b, float* pvec, float* P, float lr,
                         float lambda_att, int32_t optimizer, float* const* acc,
                         void* workspace, size_t ws_bytes, float* loss, void* stream);
+int hhfm_afm_train_step_ex(const int32_t* idx, const float* y, int64_t B, int32_t F, float* E,
+                           float* w, float* w0, int64_t features_M, int32_t k, int32_t A,
+                           float* W, float* b, float* pvec, float* P, float lr,
+                           float lambda_att, int32_t optimizer, float keep_att, float keep_afm,
+                           uint64_t seed, float* const* acc, void* workspace, size_t ws_bytes,
+                           float* loss, void* stream);
 
 /* tf.nn.top_k(scores, K) over a materialised score matrix [B][ld] (first N
  * columns), K <= 64; ids reported as global_item_base + column. */

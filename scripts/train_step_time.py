@@ -1,0 +1,105 @@
+"""Event-time of one FM and one AFM train step (the C ABI's step, all its
+kernels) at the reference's default batch (5000 rows, Frappe shape, k = A = 64,
+Adagrad), with the native extension loaded from a given folder, so that two
+builds (say a commit's and its parent's) can be alternated, a fresh process
+each.  Prints one JSON line: per case the sorted µs / step of 7 windows of 40
+steps; --drop adds FM at keep 0.5 and AFM at keep [0.8, 0.5].
+usage: python scripts/train_step_time.py LIBDIR TAG [--drop]"""
+import importlib.machinery
+import importlib.util
+import json
+import os
+import sys
+import sysconfig
+
+import numpy as np
+import torch
+
+libdir, tag = sys.argv[1], sys.argv[2]
+drop = "--drop" in sys.argv
+ext = sysconfig.get_config_var("EXT_SUFFIX")
+path = os.path.join(os.path.abspath(libdir), "_hhfm" + ext)
+loader = importlib.machinery.ExtensionFileLoader("_hhfm", path)
+spec = importlib.util.spec_from_file_location("_hhfm", path, loader=loader)
+nat = importlib.util.module_from_spec(spec)
+loader.exec_module(nat)
+
+rng = np.random.default_rng(0)
+nu, ni, ctx = 957, 4082, (7, 2, 3)
+M = nu + ni + sum(ctx)
+B, F, k, A = 5000, 5, 64, 64
+cols = [rng.integers(0, nu, B), rng.integers(nu, nu + ni, B)]
+o = nu + ni
+for c in ctx:
+    cols.append(rng.integers(o, o + c, B))
+    o += c
+dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+X = dev(np.stack(cols, 1).astype(np.int32))
+y = dev(rng.choice([1.0, -1.0], B).astype(np.float32))
+st = torch.cuda.current_stream().cuda_stream
+loss = torch.zeros(1, device="cuda")
+
+
+def params(shapes, stds):
+    par = [dev(rng.normal(0, s, sh).astype(np.float32)) for sh, s in zip(shapes, stds)]
+    acc = [torch.full_like(p, 0.1) for p in par]
+    return par, acc
+
+
+def timed(fn, reps=7, n=40):
+    for _ in range(20):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(n):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(b) * 1000.0 / n)
+    return sorted(out)
+
+
+par, acc = params([(M, k), (M,), (1,)], [0.01, 0.01, 0.01])
+ws = torch.zeros(nat.train_workspace(M, k), dtype=torch.uint8, device="cuda")
+p, a = [t.data_ptr() for t in par], [t.data_ptr() for t in acc]
+step = [0]
+
+
+def fm_plain():
+    nat.fm_train_step(X.data_ptr(), y.data_ptr(), B, F, *p, M, k, 0.1, 0.1, 0, *a,
+                      ws.data_ptr(), ws.numel(), loss.data_ptr(), st)
+
+
+def fm_drop():
+    step[0] += 1
+    nat.fm_train_step_ex(X.data_ptr(), y.data_ptr(), B, F, *p, M, k, 0.1, 0.1, 0, 0.5,
+                         2016 | step[0] << 32, *a, ws.data_ptr(), ws.numel(), loss.data_ptr(), st)
+
+
+apar, aacc = params([(M, k), (M,), (1,), (k, A), (A,), (A,), (k,)],
+                    [0.3, 0.01, 0.01, 0.125, 0.125, 1.0, 0.2])
+aws = torch.zeros(nat.afm_train_workspace(B, F, k, A, M), dtype=torch.uint8, device="cuda")
+ap, aa = [t.data_ptr() for t in apar], [t.data_ptr() for t in aacc]
+
+
+def afm_plain():
+    nat.afm_train_step(X.data_ptr(), y.data_ptr(), B, F, *ap[:3], M, k, A, *ap[3:], 0.1, 100.0, 0,
+                       aa, aws.data_ptr(), aws.numel(), loss.data_ptr(), st)
+
+
+def afm_drop():
+    step[0] += 1
+    nat.afm_train_step_ex(X.data_ptr(), y.data_ptr(), B, F, *ap[:3], M, k, A, *ap[3:], 0.1, 100.0,
+                          0, 0.8, 0.5, 2016 | step[0] << 32, aa, aws.data_ptr(), aws.numel(),
+                          loss.data_ptr(), st)
+
+
+res = {"tag": tag, "fm_keep1_us": timed(fm_plain), "afm_keep1_us": timed(afm_plain)}
+if drop:
+    res["fm_keep0.5_us"] = timed(fm_drop)
+    res["afm_keep0.8_0.5_us"] = timed(afm_drop)
+res = {k_: ([round(v, 2) for v in vs] if isinstance(vs, list) else vs) for k_, vs in res.items()}
+print(json.dumps(res))

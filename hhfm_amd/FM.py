@@ -37,13 +37,17 @@ def parse_args(dataname, factor, TopK, argv=None):
     p.add_argument("--TopK", type=int, default=TopK)
     p.add_argument("--Result", type=int, default=0)
     p.add_argument("--result_file", default="../result.txt")
+    p.add_argument("--deterministic", type=int, default=0,
+                   help="1: bit-reproducible training steps (row-ordered sums)")
     return p.parse_args(argv)
 
 
 class FM(ScoringModel):
     def __init__(self, valid_dimension, features_M, n_user, n_item, hidden_factor,
                  learning_rate, lamda_bilinear, keep, optimizer_type, batch_norm,
-                 verbose, random_seed=2016, device=None, table_dtype=torch.float32):
+                 verbose, random_seed=2016, device=None, table_dtype=torch.float32,
+                 deterministic=False):
+        self.deterministic = bool(deterministic)
         self.valid_dimension = valid_dimension
         self.n_user = n_user
         self.n_item = n_item
@@ -127,7 +131,8 @@ class Train(harness.Train):
         self.model = model if model is not None else FM(
             self.valid_dimension, self.data.features_M, self.n_user, self.n_item,
             args.hidden_factor, args.lr, args.lamda, args.keep, args.optimizer,
-            args.batch_norm, args.verbose)
+            args.batch_norm, args.verbose,
+            deterministic=bool(getattr(args, "deterministic", 0)))
 
     def train(self):
         from .training import run_training

@@ -38,13 +38,17 @@ def parse_args(dataname, factor, Topk, argv=None):
     p.add_argument("--TopK", type=int, default=Topk)
     p.add_argument("--Result", type=int, default=0)
     p.add_argument("--result_file", default="../result.txt")
+    p.add_argument("--deterministic", type=int, default=0,
+                   help="1: bit-reproducible training steps (row-ordered sums)")
     return p.parse_args(argv)
 
 
 class OUR(ScoringModel):
     def __init__(self, feature_dimension, time_dimension, features_M, n_user, n_item,
                  hidden_factor, learning_rate, lamda_bilinear, optimizer_type, context, time,
-                 random_seed=2016, device=None, table_dtype=torch.float32):
+                 random_seed=2016, device=None, table_dtype=torch.float32,
+                 deterministic=False):
+        self.deterministic = bool(deterministic)
         self.feature_dimension = feature_dimension
         self.time_dimension = time_dimension
         self.n_user = n_user
@@ -144,7 +148,7 @@ class Train(harness.Train):
         self.model = model if model is not None else OUR(
             self.feature_dimension, self.time_dimension, self.features_M, self.n_user,
             self.n_item, args.hidden_factor, args.lr, args.lamda, args.optimizer,
-            self.context, self.time)
+            self.context, self.time, deterministic=bool(getattr(args, "deterministic", 0)))
 
     def train(self):
         from .training import run_training_hhfm

@@ -445,6 +445,45 @@ PYBIND11_MODULE(_hhfm, m) {
           check(rc, "hhfm_hhfm_train_step");
         });
 
+  // the deterministic steps (include/hhfm.h "Deterministic training steps")
+  m.def("train_det_scratch", [](int64_t B, int occ_per_row, int k, int64_t M) {
+    size_t n = 0;
+    check(hhfm_train_det_scratch(B, occ_per_row, k, M, &n), "hhfm_train_det_scratch");
+    return n;
+  });
+
+  m.def("fm_train_step_det",
+        [](uptr idx, uptr y, int64_t B, int F, uptr E, uptr w, uptr w0, int64_t M, int k,
+           float lr, float lam, int opt, float keep, uint64_t seed, uptr accE, uptr accw,
+           uptr accw0, uptr ws, size_t ws_bytes, uptr scratch, size_t scratch_bytes, uptr loss,
+           uptr stream) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_fm_train_step_det(P<const int32_t>(idx), P<const float>(y), B, F,
+                                        P<float>(E), P<float>(w), P<float>(w0), M, k, lr, lam,
+                                        opt, keep, seed, P<float>(accE), P<float>(accw),
+                                        P<float>(accw0), P<void>(ws), ws_bytes, P<void>(scratch),
+                                        scratch_bytes, P<float>(loss), P<void>(stream));
+          }
+          check(rc, "hhfm_fm_train_step_det");
+        });
+
+  m.def("hhfm_train_step_det",
+        [](uptr X, uptr Neg, int64_t B, int ncols, int c0, int c1, int t0, int t1, int NG,
+           uptr E, int64_t M, int k, float lr, float lam, int opt, uptr accE, uptr ws,
+           size_t ws_bytes, uptr scratch, size_t scratch_bytes, uptr loss, uptr stream) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_hhfm_train_step_det(P<const int32_t>(X), P<const int32_t>(Neg), B, ncols,
+                                          c0, c1, t0, t1, NG, P<float>(E), M, k, lr, lam, opt,
+                                          P<float>(accE), P<void>(ws), ws_bytes, P<void>(scratch),
+                                          scratch_bytes, P<float>(loss), P<void>(stream));
+          }
+          check(rc, "hhfm_hhfm_train_step_det");
+        });
+
   m.def("dfm_train_workspace",
         [](int64_t B, int F, int k, int64_t M, std::vector<int32_t> dims) {
           size_t ws = 0;

@@ -30,6 +30,8 @@
 // the plan functions: fm_train_plan (FM and HHFM), dfm_train_plan and
 // afm_train_plan (their shared persistent prefix in TrainWs).  The optimizer
 // tail every step ends with is optimizer_tail.
+#include <hipcub/hipcub.hpp>
+
 #include <cfloat>
 #include <initializer_list>
 #include <iterator>
@@ -225,6 +227,10 @@ struct OptStep {
   int sparse;              // the variable's TF gradient is an IndexedSlices
 };
 
+// ORDERED (the deterministic steps): `sumsq` is an array and every wave stores
+// its partial at its global wave index — the grid is a function of n alone —
+// for det_sumsq to add in ascending index; else one float atomic per wave.
+template <bool ORDERED>
 __global__ __launch_bounds__(256) void optimizer_apply(float* __restrict__ var,
                                                        float* __restrict__ grad,
                                                        float* __restrict__ state, int64_t n,
@@ -272,8 +278,32 @@ __global__ __launch_bounds__(256) void optimizer_apply(float* __restrict__ var,
   }
   if (sumsq) {
     ss = group_sum<kWave>(ss);
-    if ((threadIdx.x & 63) == 0) atomicAdd(sumsq, ss);
+    if ((threadIdx.x & 63) == 0) {
+      if constexpr (ORDERED)
+        sumsq[((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave] = ss;
+      else
+        atomicAdd(sumsq, ss);
+    }
   }
+}
+
+// Σvar² of a deterministic step: the waves' partials added in ascending index
+// in double by one thread (the others stage them through LDS), rounded once.
+constexpr int kDetStage = 4096;
+
+__global__ __launch_bounds__(256) void det_sumsq(const float* __restrict__ part, int64_t n,
+                                                 float* __restrict__ out) {
+  __shared__ float buf[kDetStage];
+  double s = 0.0;
+  for (int64_t base = 0; base < n; base += kDetStage) {
+    const int m = (int)(n - base < kDetStage ? n - base : kDetStage);
+    for (int j = threadIdx.x; j < m; j += blockDim.x) buf[j] = part[base + j];
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int j = 0; j < m; ++j) s += (double)buf[j];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = (float)s;
 }
 
 // after every variable's update: β1^t, β2^t -> β1^(t+1), β2^(t+1) (AdamOptimizer._finish).
@@ -311,6 +341,9 @@ static int grid_for_n(int64_t n) {
   int64_t g = (n + 255) / 256;
   return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
 }
+
+// waves of optimizer_apply's grid over n elements = Σvar² partials it stores when ORDERED
+static int64_t det_sumsq_floats(int64_t n) { return (int64_t)grid_for_n(n) * (256 / kWave); }
 
 static bool opt_ok(int opt) {
   return opt == HHFM_OPT_ADAGRAD || opt == HHFM_OPT_SGD || opt == HHFM_OPT_MOMENTUM ||
@@ -351,10 +384,13 @@ struct IdList {
 // `touched` for the sparse variables (and unmarked afterwards: the mask is
 // left zeroed), one optimizer_apply per variable in list order, Adam's powers
 // advance, and finish_loss writes loss = data loss + loss_lam·Σvar²/2 and
-// clears the scalars.  Returns hipGetLastError().
+// clears the scalars.  With `ss_part` (the deterministic steps; one float per
+// wave of every sumsq variable's grid, det_sumsq_floats) Σvar² is the ordered
+// sum of det_sumsq instead of float atomics.  Returns hipGetLastError().
 static int optimizer_tail(const OptVar* vars, int nvars, std::initializer_list<IdList> ids,
                           int64_t M, int opt, float lr, float* scal, uint8_t* touched,
-                          float loss_lam, float* loss, hipStream_t st) {
+                          float loss_lam, float* loss, hipStream_t st,
+                          float* ss_part = nullptr) {
   bool mark = false;
   for (int i = 0; i < nvars; ++i) mark |= opt == HHFM_OPT_MOMENTUM && vars[i].sparse;
   auto set_mask = [&](uint8_t val) {
@@ -364,12 +400,21 @@ static int optimizer_tail(const OptVar* vars, int nvars, std::initializer_list<I
                            touched, val);
   };
   set_mask(1);
+  int64_t nss = 0;   // partials written so far
   for (int i = 0; i < nvars; ++i) {
     const OptVar& v = vars[i];
     OptStep o{opt, lr, scal + kScalAdam, v.sparse ? touched : nullptr, v.rowlen, v.sparse ? 1 : 0};
-    hipLaunchKernelGGL(optimizer_apply, dim3(grid_for_n(v.n)), dim3(256), 0, st, v.var, v.grad,
-                       v.slot, v.n, v.lam, o, v.sumsq ? scal + kScalSumSq : nullptr);
+    if (ss_part) {
+      hipLaunchKernelGGL(optimizer_apply<true>, dim3(grid_for_n(v.n)), dim3(256), 0, st, v.var,
+                         v.grad, v.slot, v.n, v.lam, o, v.sumsq ? ss_part + nss : nullptr);
+      if (v.sumsq) nss += det_sumsq_floats(v.n);
+    } else {
+      hipLaunchKernelGGL(optimizer_apply<false>, dim3(grid_for_n(v.n)), dim3(256), 0, st, v.var,
+                         v.grad, v.slot, v.n, v.lam, o, v.sumsq ? scal + kScalSumSq : nullptr);
+    }
   }
+  if (nss > 0)
+    hipLaunchKernelGGL(det_sumsq, dim3(1), dim3(256), 0, st, ss_part, nss, scal + kScalSumSq);
   set_mask(0);
   if (opt == HHFM_OPT_ADAM)
     hipLaunchKernelGGL(adam_advance, dim3(1), dim3(1), 0, st, scal + kScalAdam);
@@ -392,6 +437,465 @@ static FmTrainPlan fm_train_plan(int64_t M, int k) {
   p.off_touch = p.off_scal + kScalFloats;
   p.bytes = (size_t)p.off_touch * 4 + (((size_t)M + 255) & ~size_t(255));
   return p;
+}
+
+// ---------------------------------------------------------------------------
+// Deterministic FM / HHFM steps (hhfm_fm_train_step_det, hhfm_hhfm_train_step_det):
+// no float atomics, every sum's order a function of the batch alone
+// (include/hhfm.h "Deterministic training steps" states the orders).
+//   row pass      *_train_rows_det: the forward of the row kernels above, one
+//                 wave per row, which STORES per row what the scatter needs
+//                 (FM: g, S[c] = Σ_f E[x_f][c]; HHFM: g, gt, the tie mask,
+//                 h[c], dh[c]) and the row's loss
+//   grouping      det_keys -> a stable radix sort of (clamped id, occurrence
+//                 o = b·S + slot) -> det_runs: the first position of every
+//                 distinct id (compacted with an integer atomic: the order of
+//                 the run list decides nothing)
+//   segment pass  det_segments<C>: one wave per distinct id walks the id's
+//                 occurrences in ascending o and adds their contributions in
+//                 fp32, lane = column; one plain store per element of dE / dw
+//   scalars       det_scalars (g and the loss), det_sumsq (Σvar²)
+// The contribution of an occurrence is a functor C (FmContrib, HhfmContrib);
+// another model's scatter plugs in there.
+// ---------------------------------------------------------------------------
+static size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
+
+static int det_key_bits(int64_t M) {
+  int b = 1;
+  while (b < 31 && (int64_t(1) << b) < M) ++b;
+  return b;
+}
+
+// Byte offsets of the per-batch scratch (nothing in it outlives a step).
+struct DetPlan {
+  int n, bits;   // occurrences B·S, key bits of the sort
+  size_t keys_in, keys_out, vals_in, vals_out, runs, nruns, rowvec, g, gt, mask, loss, sspart,
+      tmp, tmp_bytes, bytes;
+};
+
+static bool det_plan(int64_t B, int S, int k, int64_t M, DetPlan& p) {
+  if (B < 0 || S < 1 || k < 1 || M < 1) return false;
+  if (B > 0x7fffffff || B * S > 0x7fffffff) return false;   // the sort counts in int
+  p = DetPlan{};
+  p.n = (int)(B * S);
+  p.bits = det_key_bits(M);
+  // The sort's temporary storage.  hipCUB's own size query needs a device (it
+  // picks a tuning by architecture) and this plan must not, so an upper bound
+  // is reserved instead: a second copy of the n keys and of the n values
+  // (8n bytes), one 4-byte look-back state per digit and block of >= 256
+  // items (<= 4n + 1 KiB) and at most 32 histograms of 256 8-byte bins
+  // (64 KiB), with slack.  det_scatter asks hipCUB for the real figure and
+  // refuses the step should it ever be larger.
+  p.tmp_bytes = p.n > 0 ? 16 * (size_t)p.n + (size_t(256) << 10) : 0;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t r = off;
+    off += al256(bytes);
+    return r;
+  };
+  p.keys_in = take((size_t)p.n * 4);
+  p.keys_out = take((size_t)p.n * 4);
+  p.vals_in = take((size_t)p.n * 4);
+  p.vals_out = take((size_t)p.n * 4);
+  p.runs = take((size_t)p.n * 4);
+  p.nruns = take(4);
+  p.rowvec = take((size_t)B * 2 * k * 4);   // FM uses [B][k], HHFM [B][2k]
+  p.g = take((size_t)B * 4);
+  p.gt = take((size_t)B * 4);
+  p.mask = take((size_t)B * 4);
+  p.loss = take((size_t)B * 8);
+  p.sspart = take((size_t)det_sumsq_floats(M * k) * 4);
+  p.tmp = take(p.tmp_bytes);
+  p.bytes = off;
+  return true;
+}
+
+// FM's row pass: fm_train_rows's forward (the same expressions in the same
+// order), then S_b[c] = Σ_f E[x_f][c] (Sb [B][k]; under dropout the mask's
+// bin_b[c] follows it, [B][k] more), g_b and the row's loss r²/2 stored.
+template <bool DROP>
+__global__ __launch_bounds__(256) void fm_train_rows_det(
+    const int32_t* __restrict__ idx, const float* __restrict__ y, int64_t B, int F,
+    const float* __restrict__ E, const float* __restrict__ w, const float* __restrict__ w0,
+    int64_t M, int k, float* __restrict__ gb, double* __restrict__ lossb,
+    float* __restrict__ Sb, DropoutArgs dr) {
+  const int l = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  for (int64_t b = wave; b < B; b += nwave) {
+    const int32_t* x = idx + b * F;
+    float t = 0.f;
+    [[maybe_unused]] LaneDropout ld;
+    for (int c = l; c < k; c += kWave) {
+      float s = 0.f, q = 0.f;
+      for (int f = 0; f < F; ++f) {
+        const float v = E[(int64_t)clamp_id(x[f], M) * k + c];
+        s += v;
+        q += v * v;
+      }
+      if constexpr (DROP) {
+        const float bin = ld.binary(dr, dr.keep0, kDropSiteFm, b, c);
+        t += 0.5f * (s * s - q) / dr.keep0 * bin;
+        Sb[(B + b) * k + c] = bin;
+      } else {
+        t += 0.5f * (s * s - q);
+      }
+      Sb[b * k + c] = s;
+    }
+    t = group_sum<kWave>(t);
+    float fb = 0.f;
+    for (int f = 0; f < F; ++f) fb += w[clamp_id(x[f], M)];
+    const float out = (t + fb) + w0[0];
+    const float r = y[b] - out;
+    if (l == 0) {
+      gb[b] = -r;
+      lossb[b] = 0.5 * ((double)r * (double)r);
+    }
+  }
+}
+
+// HHFM's row pass: hhfm_train_rows's forward, then per row g, gt = g / ties,
+// bit j of the mask = negative j is a tied maximum, h[c] and
+// dh[c] = g·it − gt·nsum ([B][2k]: h, then dh) and the loss −log σ(z).
+__global__ __launch_bounds__(256) void hhfm_train_rows_det(
+    const int32_t* __restrict__ X, const int32_t* __restrict__ Neg, int64_t B, int ncols,
+    int c0, int c1, int t0, int t1, int NG, const float* __restrict__ E, int64_t M, int k,
+    float* __restrict__ gb, float* __restrict__ gtb, uint32_t* __restrict__ maskb,
+    double* __restrict__ lossb, float* __restrict__ HV) {
+  const int l = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  for (int64_t b = wave; b < B; b += nwave) {
+    const int32_t* x = X + b * ncols;
+    const int32_t* ng = Neg + b * NG;
+    const int64_t iu = clamp_id(x[0], M), ii = clamp_id(x[1], M);
+    auto hval = [&](int c) {
+      float h = E[iu * k + c];
+      if (c1 > c0) {
+        float s = 0.f;
+        for (int j = c0; j < c1; ++j) s += E[(int64_t)clamp_id(x[j], M) * k + c];
+        h = h + s;
+      }
+      if (t1 > t0) {
+        float s = 0.f;
+        for (int j = t0; j < t1; ++j) s += E[(int64_t)clamp_id(x[j], M) * k + c];
+        h = h + s;
+      }
+      return h;
+    };
+    float pos = 0.f;
+    for (int c = l; c < k; c += kWave) pos += hval(c) * E[ii * k + c];
+    pos = group_sum<kWave>(pos);
+    float negv[kMaxNeg];
+    float mx = -__builtin_huge_valf();
+#pragma unroll
+    for (int j = 0; j < kMaxNeg; ++j) {
+      negv[j] = -__builtin_huge_valf();
+      if (j < NG) {
+        float v = 0.f;
+        const int64_t in = clamp_id(ng[j], M);
+        for (int c = l; c < k; c += kWave) v += hval(c) * E[in * k + c];
+        v = group_sum<kWave>(v);
+        negv[j] = v;
+        mx = fmaxf(mx, v);
+      }
+    }
+    int nt = 0;
+    uint32_t tied = 0;
+#pragma unroll
+    for (int j = 0; j < kMaxNeg; ++j) {
+      nt += (j < NG && negv[j] == mx);
+      tied |= (uint32_t)(j < NG && negv[j] == mx) << j;
+    }
+    const float z = pos - mx;
+    const float sg = 1.f / (1.f + expf(-z));
+    const float g = sg - 1.f;
+    const float gt = g / (float)nt;
+    for (int c = l; c < k; c += kWave) {
+      const float h = hval(c);
+      const float it = E[ii * k + c];
+      float nsum = 0.f;
+#pragma unroll
+      for (int j = 0; j < kMaxNeg; ++j)
+        if (j < NG && negv[j] == mx) nsum += E[(int64_t)clamp_id(ng[j], M) * k + c];
+      const float dh = g * it - gt * nsum;
+      HV[b * 2 * k + c] = h;
+      HV[b * 2 * k + k + c] = dh;
+    }
+    if (l == 0) {
+      gb[b] = g;
+      gtb[b] = gt;
+      maskb[b] = tied;
+      lossb[b] = (double)-logf(sg);
+    }
+  }
+}
+
+// Where the id of occurrence (b, slot) comes from.  FM (Neg null): slot = the
+// field, S = ncols.  HHFM: item, negatives 0..NG-1, user, context columns,
+// time columns — the order hhfm_train_rows scatters in.
+struct OccSource {
+  const int32_t* X;
+  const int32_t* Neg;
+  int ncols, NG, c0, c1, t0, t1;
+};
+
+HHFM_DEV int32_t occ_id(const OccSource& s, int64_t b, int slot) {
+  const int32_t* x = s.X + b * s.ncols;
+  if (!s.Neg) return x[slot];
+  if (slot == 0) return x[1];
+  if (slot <= s.NG) return s.Neg[b * s.NG + slot - 1];
+  if (slot == s.NG + 1) return x[0];
+  const int j = slot - s.NG - 2, nc = s.c1 - s.c0;
+  return x[j < nc ? s.c0 + j : s.t0 + (j - nc)];
+}
+
+// keys[o] = the clamped id of occurrence o, vals[o] = o; clears the run counter
+__global__ __launch_bounds__(256) void det_keys(OccSource s, int S, int n, int64_t M,
+                                                uint32_t* __restrict__ keys,
+                                                int32_t* __restrict__ vals,
+                                                int32_t* __restrict__ nruns) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) nruns[0] = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int b = (int)(i / S);
+    keys[i] = (uint32_t)clamp_id(occ_id(s, b, (int)(i - (int64_t)b * S)), M);
+    vals[i] = (int32_t)i;
+  }
+}
+
+// runs[...] = every position of the sorted keys at which a new id starts
+__global__ __launch_bounds__(256) void det_runs(const uint32_t* __restrict__ keys, int n,
+                                                int32_t* __restrict__ runs,
+                                                int32_t* __restrict__ nruns) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    if (i == 0 || keys[i] != keys[i - 1]) runs[atomicAdd(nruns, 1)] = (int32_t)i;
+}
+
+// the value lane `lane` (wave-uniform) holds
+HHFM_DEV int lane_i(int x, int lane) { return __builtin_amdgcn_readlane(x, lane); }
+HHFM_DEV float lane_f(float x, int lane) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), lane));
+}
+
+// A contribution functor C tells det_segments what an occurrence adds:
+//   Occ load(o)            the occurrence's row data (each lane loads another o)
+//   Occ lane(occ, u)       lane u's Occ in every lane
+//   bool value(occ, c, e, out)   the contribution to column c of the id's row
+//                          (e = E[id][c]); false = it adds nothing.  No
+//                          branch: det_segments issues a group's loads together
+//   kBias, bias(occ)       the contribution to dw[id], where the model has one
+//
+// FM's, o = b·F + f: gc·(S_b[c] − e), gc = g_b (· bin / keep under dropout, the
+// row pass's mask read back; a dropped column adds nothing); dw: g_b.
+template <bool DROP>
+struct FmContrib {
+  static constexpr bool kBias = true;
+  const float* g;
+  const float* S;   // S [B][k], then (DROP) bin [B][k]
+  int64_t B;
+  int F, k;
+  float keep;
+  struct Occ {
+    int b;
+    float g;
+  };
+  HHFM_DEV Occ load(int o) const {
+    const int b = o / F;
+    return Occ{b, g[b]};
+  }
+  HHFM_DEV Occ lane(const Occ& oc, int u) const { return Occ{lane_i(oc.b, u), lane_f(oc.g, u)}; }
+  HHFM_DEV float bias(const Occ& oc) const { return oc.g; }
+  HHFM_DEV bool value(const Occ& oc, int c, float e, float& out) const {
+#pragma clang fp contract(off)
+    float gc = oc.g;
+    bool kept = true;
+    if constexpr (DROP) {
+      const float bin = S[((int64_t)B + oc.b) * k + c];
+      kept = bin != 0.f;
+      gc = oc.g * bin / keep;
+    }
+    out = gc * (S[(int64_t)oc.b * k + c] - e);
+    return kept;
+  }
+};
+
+// HHFM's, o = b·S + slot: slot 0 (item) g·h; slots 1..NG (negative j) −gt·h
+// when j is a tied maximum, else nothing; the other slots dh.
+struct HhfmContrib {
+  static constexpr bool kBias = false;
+  const float* g;
+  const float* gt;
+  const uint32_t* mask;
+  const float* HV;
+  int S, NG, k;
+  enum { kNothing = 0, kTimesH = 1, kDh = 2 };
+  struct Occ {
+    int b, kind;
+    float coef;   // what multiplies h
+  };
+  HHFM_DEV Occ load(int o) const {
+    const int b = o / S, slot = o - b * S;
+    if (slot == 0) return Occ{b, kTimesH, g[b]};
+    if (slot <= NG) return Occ{b, (int)((mask[b] >> (slot - 1)) & 1u), -gt[b]};
+    return Occ{b, kDh, 0.f};
+  }
+  HHFM_DEV Occ lane(const Occ& oc, int u) const {
+    return Occ{lane_i(oc.b, u), lane_i(oc.kind, u), lane_f(oc.coef, u)};
+  }
+  HHFM_DEV float bias(const Occ&) const { return 0.f; }
+  HHFM_DEV bool value(const Occ& oc, int c, float, float& out) const {
+#pragma clang fp contract(off)
+    const float v = HV[(int64_t)oc.b * 2 * k + (oc.kind == kDh ? k : 0) + c];
+    out = oc.kind == kDh ? v : oc.coef * v;
+    return oc.kind != kNothing;
+  }
+};
+
+// One wave per distinct id (grid-stride over the run list), lane = column
+// (strided for k > 64).  The id's occurrences lie consecutively in `vals`, in
+// ascending o.  The wave takes 64 at a time: lane u loads occurrence u's row
+// data (the next 64 are requested before these are consumed), then the
+// occurrences are visited in order, kDetAhead at a time: their row vectors
+// are loaded together — the addresses come from the sorted list — and only
+// the chain of fp32 adds acc = acc + contribution is serial, the first
+// contribution starting the sum.  An id whose occurrences all add nothing
+// stores 0.
+constexpr int kDetAhead = 32;
+
+template <class C>
+__global__ __launch_bounds__(256) void det_segments(
+    const uint32_t* __restrict__ keys, const int32_t* __restrict__ vals, int n,
+    const int32_t* __restrict__ runs, const int32_t* __restrict__ nruns,
+    const float* __restrict__ E, int k, float* __restrict__ dE, float* __restrict__ dw,
+    C contrib) {
+  using Occ = typename C::Occ;
+  const int l = threadIdx.x & 63;
+  const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) / kWave);
+  const int nwave = (int)((gridDim.x * blockDim.x) / kWave);
+  const int nr = nruns[0];
+  for (int r = wave; r < nr; r += nwave) {
+    const int start = __builtin_amdgcn_readfirstlane(runs[r]);
+    const uint32_t id = (uint32_t)__builtin_amdgcn_readfirstlane((int)keys[start]);
+    // lane l's occurrence of the 64 from `base`; -> how many of them are the id's
+    auto fetch = [&](int64_t base, Occ& mine) {
+      const int64_t j = base + l;
+      const bool ok = j < n && keys[j] == id;
+      mine = contrib.load(ok ? vals[j] : 0);
+      return (int)__popcll(__ballot(ok));   // the id's occurrences are a prefix
+    };
+    for (int cb = 0; cb < k; cb += kWave) {
+      const int c = cb + l;
+      const bool live = c < k;
+      const float e = live ? E[(int64_t)id * k + c] : 0.f;
+      float acc = 0.f, accw = 0.f;
+      bool have = false, havew = false;
+      Occ mine, next;
+      int cnt = fetch(start, mine);
+      for (int64_t base = start;; base += kWave) {
+        const int cntn = cnt == kWave ? fetch(base + kWave, next) : 0;
+        for (int u0 = 0; u0 < cnt; u0 += kDetAhead) {
+          // straight-line: every load of the group is issued before the first
+          // add (a slot past the id's last occurrence re-reads that one, a
+          // lane past column k reads column 0; both are masked out below)
+          float cv[kDetAhead];
+          bool hv[kDetAhead];
+#pragma unroll
+          for (int u = 0; u < kDetAhead; ++u) {
+            const bool in = u0 + u < cnt;
+            const Occ oc = contrib.lane(mine, in ? u0 + u : cnt - 1);
+            const bool adds = contrib.value(oc, live ? c : 0, e, cv[u]);
+            hv[u] = in & live & adds;
+          }
+#pragma unroll
+          for (int u = 0; u < kDetAhead; ++u) {
+#pragma clang fp contract(off)
+            const float sum = acc + cv[u];
+            acc = hv[u] ? (have ? sum : cv[u]) : acc;
+            have |= hv[u];
+          }
+          if (C::kBias && cb == 0) {
+#pragma unroll
+            for (int u = 0; u < kDetAhead; ++u) {
+#pragma clang fp contract(off)
+              const bool in = u0 + u < cnt;
+              const float gb = contrib.bias(contrib.lane(mine, in ? u0 + u : cnt - 1));
+              const float sum = accw + gb;
+              accw = in ? (havew ? sum : gb) : accw;
+              havew |= in;
+            }
+          }
+        }
+        if (cntn == 0) break;
+        mine = next;
+        cnt = cntn;
+      }
+      if (live) dE[(int64_t)id * k + c] = have ? acc : 0.f;
+      if (C::kBias && cb == 0 && l == 0) dw[id] = accw;
+    }
+  }
+}
+
+// The step's scalars in a fixed order: thread t of one 256-thread workgroup
+// adds rows t, t + 256, ... ascending (g in float — null for HHFM, which has
+// no bias — the loss in double), thread 0 the 256 partials in ascending t.
+__global__ __launch_bounds__(256) void det_scalars(const float* __restrict__ gb,
+                                                   const double* __restrict__ lossb, int64_t B,
+                                                   float* __restrict__ scal) {
+  __shared__ float sg[256];
+  __shared__ double sl[256];
+  float a = 0.f;
+  double d = 0.0;
+  for (int64_t b = threadIdx.x; b < B; b += 256) {
+    if (gb) a += gb[b];
+    d += lossb[b];
+  }
+  sg[threadIdx.x] = a;
+  sl[threadIdx.x] = d;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float A = 0.f;
+    double D = 0.0;
+    for (int t = 0; t < 256; ++t) {
+      A += sg[t];
+      D += sl[t];
+    }
+    if (gb) scal[kScalBiasGrad] = A;
+    scal[kScalDataLoss] = (float)D;
+  }
+}
+
+// grouping + segment pass + scalars of one deterministic step (n > 0); the
+// row pass has run (it wrote only scratch: a refusal here leaves every parameter
+// untouched).  Returns 0, a hipError_t or HHFM_EWORKSPACE.
+template <class C>
+static int det_scatter(const DetPlan& p, char* sc, const OccSource& src, int S, int64_t B,
+                       int64_t M, const float* E, int k, float* dE, float* dw, const float* gb,
+                       float* scal, const C& contrib, hipStream_t st) {
+  uint32_t* kin = reinterpret_cast<uint32_t*>(sc + p.keys_in);
+  uint32_t* kout = reinterpret_cast<uint32_t*>(sc + p.keys_out);
+  int32_t* vin = reinterpret_cast<int32_t*>(sc + p.vals_in);
+  int32_t* vout = reinterpret_cast<int32_t*>(sc + p.vals_out);
+  int32_t* runs = reinterpret_cast<int32_t*>(sc + p.runs);
+  int32_t* nruns = reinterpret_cast<int32_t*>(sc + p.nruns);
+  const int gn = grid_for_n(p.n);
+  size_t tmp = 0;
+  hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, kin, kout, vin, vout, p.n, 0,
+                                                    p.bits, st);
+  if (e != hipSuccess) return (int)e;
+  if (tmp > p.tmp_bytes) return HHFM_EWORKSPACE;
+  hipLaunchKernelGGL(det_keys, dim3(gn), dim3(256), 0, st, src, S, p.n, M, kin, vin, nruns);
+  e = hipcub::DeviceRadixSort::SortPairs(sc + p.tmp, tmp, kin, kout, vin, vout, p.n, 0, p.bits,
+                                         st);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(det_runs, dim3(gn), dim3(256), 0, st, kout, p.n, runs, nruns);
+  const int64_t ids = M < p.n ? M : p.n;   // at most this many distinct ids
+  hipLaunchKernelGGL(det_segments<C>, dim3(grid_for_n(ids * kWave)), dim3(256), 0, st, kout, vout,
+                     p.n, runs, nruns, E, k, dE, dw, contrib);
+  hipLaunchKernelGGL(det_scalars, dim3(1), dim3(256), 0, st, gb,
+                     reinterpret_cast<const double*>(sc + p.loss), B, scal);
+  return (int)hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
@@ -1027,12 +1531,14 @@ extern "C" int hhfm_fm_train_step(const int32_t* idx, const float* y, int64_t B,
                                accE, accw, accw0, workspace, ws_bytes, loss, stream);
 }
 
-extern "C" int hhfm_fm_train_step_ex(const int32_t* idx, const float* y, int64_t B, int32_t F,
-                                     float* E, float* w, float* w0, int64_t features_M,
-                                     int32_t k, float lr, float lam, int32_t optimizer,
-                                     float keep, uint64_t seed, float* accE, float* accw,
-                                     float* accw0, void* workspace, size_t ws_bytes, float* loss,
-                                     void* stream) {
+// The FM step: the default path (det false; scratch unused), or the
+// deterministic one on `scratch` (hhfm_train_det_scratch bytes).
+static int fm_train_step_impl(const int32_t* idx, const float* y, int64_t B, int32_t F, float* E,
+                              float* w, float* w0, int64_t features_M, int32_t k, float lr,
+                              float lam, int32_t optimizer, float keep, uint64_t seed,
+                              float* accE, float* accw, float* accw0, void* workspace,
+                              size_t ws_bytes, bool det, void* scratch, size_t scratch_bytes,
+                              float* loss, void* stream) {
   if (B < 0 || F < 1 || k < 1 || features_M < 1 || !keep_ok(keep)) return HHFM_EINVAL;
   if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
   if (!E || !w || !w0 || !loss || !workspace) return HHFM_EINVAL;
@@ -1041,14 +1547,32 @@ extern "C" int hhfm_fm_train_step_ex(const int32_t* idx, const float* y, int64_t
   if (!slots_ok(optimizer, acc, 3)) return HHFM_EINVAL;
   const FmTrainPlan p = fm_train_plan(features_M, k);
   if (ws_bytes < p.bytes) return HHFM_EWORKSPACE;
+  DetPlan d{};
+  if (det && (!det_plan(B, F, k, features_M, d) || !scratch || scratch_bytes < d.bytes))
+    return HHFM_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   float* ws = reinterpret_cast<float*>(workspace);
   float* scal = ws + p.off_scal;
-  if (B > 0) {
+  char* sc = reinterpret_cast<char*>(scratch);
+  const DropoutArgs dr = dropout_args(keep, 1.f, seed);
+  if (B > 0 && !det) {
     auto rows = keep < 1.f ? fm_train_rows<true> : fm_train_rows<false>;
     hipLaunchKernelGGL(rows, dim3(grid_for_n(B * 64)), dim3(256), 0, st, idx, y, B, F, E, w, w0,
-                       features_M, k, ws + p.off_dE, ws + p.off_dw, scal,
-                       dropout_args(keep, 1.f, seed));
+                       features_M, k, ws + p.off_dE, ws + p.off_dw, scal, dr);
+  } else if (B > 0) {
+    float* gb = reinterpret_cast<float*>(sc + d.g);
+    float* Sb = reinterpret_cast<float*>(sc + d.rowvec);
+    auto rows = keep < 1.f ? fm_train_rows_det<true> : fm_train_rows_det<false>;
+    hipLaunchKernelGGL(rows, dim3(grid_for_n(B * 64)), dim3(256), 0, st, idx, y, B, F, E, w, w0,
+                       features_M, k, gb, reinterpret_cast<double*>(sc + d.loss), Sb, dr);
+    const OccSource src{idx, nullptr, F, 0, 0, 0, 0, 0};
+    const int rc = keep < 1.f
+                       ? det_scatter(d, sc, src, F, B, features_M, E, k, ws + p.off_dE,
+                                     ws + p.off_dw, gb, scal, FmContrib<true>{gb, Sb, B, F, k, keep}, st)
+                       : det_scatter(d, sc, src, F, B, features_M, E, k, ws + p.off_dE,
+                                     ws + p.off_dw, gb, scal, FmContrib<false>{gb, Sb, B, F, k, keep},
+                                     st);
+    if (rc != 0) return rc;
   }
   // sparse gradients (FM.py:123-126): w's always (embedding_lookup only), E's
   // when λ = 0 (no dense l2 term); w0 and the λ > 0 table are dense
@@ -1058,15 +1582,47 @@ extern "C" int hhfm_fm_train_step_ex(const int32_t* idx, const float* y, int64_t
       {w0, scal + kScalBiasGrad, accw0, 1, 0.f, 1, false, false}};
   uint8_t* touched = reinterpret_cast<uint8_t*>(ws + p.off_touch);
   return optimizer_tail(vars, (int)std::size(vars), {{idx, B * F}}, features_M, optimizer, lr,
-                        scal, touched, lam, loss, st);
+                        scal, touched, lam, loss, st,
+                        det ? reinterpret_cast<float*>(sc + d.sspart) : nullptr);
 }
 
-extern "C" int hhfm_hhfm_train_step(const int32_t* X, const int32_t* Neg, int64_t B,
-                                    int32_t ncols, int32_t ctx_begin, int32_t ctx_end,
-                                    int32_t time_begin, int32_t time_end, int32_t NG, float* E,
-                                    int64_t features_M, int32_t k, float lr, float lam,
-                                    int32_t optimizer, float* accE, void* workspace,
-                                    size_t ws_bytes, float* loss, void* stream) {
+extern "C" int hhfm_fm_train_step_ex(const int32_t* idx, const float* y, int64_t B, int32_t F,
+                                     float* E, float* w, float* w0, int64_t features_M,
+                                     int32_t k, float lr, float lam, int32_t optimizer,
+                                     float keep, uint64_t seed, float* accE, float* accw,
+                                     float* accw0, void* workspace, size_t ws_bytes, float* loss,
+                                     void* stream) {
+  return fm_train_step_impl(idx, y, B, F, E, w, w0, features_M, k, lr, lam, optimizer, keep, seed,
+                            accE, accw, accw0, workspace, ws_bytes, false, nullptr, 0, loss,
+                            stream);
+}
+
+extern "C" int hhfm_fm_train_step_det(const int32_t* idx, const float* y, int64_t B, int32_t F,
+                                      float* E, float* w, float* w0, int64_t features_M,
+                                      int32_t k, float lr, float lam, int32_t optimizer,
+                                      float keep, uint64_t seed, float* accE, float* accw,
+                                      float* accw0, void* workspace, size_t ws_bytes,
+                                      void* scratch, size_t scratch_bytes, float* loss,
+                                      void* stream) {
+  return fm_train_step_impl(idx, y, B, F, E, w, w0, features_M, k, lr, lam, optimizer, keep, seed,
+                            accE, accw, accw0, workspace, ws_bytes, true, scratch, scratch_bytes,
+                            loss, stream);
+}
+
+extern "C" int hhfm_train_det_scratch(int64_t B, int32_t occ_per_row, int32_t k,
+                                      int64_t features_M, size_t* bytes) {
+  DetPlan d;
+  if (!bytes || !det_plan(B, occ_per_row, k, features_M, d)) return HHFM_EINVAL;
+  *bytes = d.bytes;
+  return HHFM_OK;
+}
+
+static int hhfm_train_step_impl(const int32_t* X, const int32_t* Neg, int64_t B, int32_t ncols,
+                                int32_t ctx_begin, int32_t ctx_end, int32_t time_begin,
+                                int32_t time_end, int32_t NG, float* E, int64_t features_M,
+                                int32_t k, float lr, float lam, int32_t optimizer, float* accE,
+                                void* workspace, size_t ws_bytes, bool det, void* scratch,
+                                size_t scratch_bytes, float* loss, void* stream) {
   if (B < 0 || ncols < 2 || NG < 1 || k < 1 || features_M < 1) return HHFM_EINVAL;
   if (NG > kMaxNeg) return HHFM_EUNSUPPORTED;
   if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
@@ -1075,18 +1631,63 @@ extern "C" int hhfm_hhfm_train_step(const int32_t* X, const int32_t* Neg, int64_
   if (!slots_ok(optimizer, &accE, 1)) return HHFM_EINVAL;
   const FmTrainPlan p = fm_train_plan(features_M, k);   // dw stays unused
   if (ws_bytes < p.bytes) return HHFM_EWORKSPACE;
+  // occurrences per row: item, negatives, user, context and time columns
+  const int nc = ctx_end > ctx_begin ? ctx_end - ctx_begin : 0;
+  const int nt = time_end > time_begin ? time_end - time_begin : 0;
+  const int S = 2 + NG + nc + nt;
+  DetPlan d{};
+  if (det && (!det_plan(B, S, k, features_M, d) || !scratch || scratch_bytes < d.bytes))
+    return HHFM_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   float* ws = reinterpret_cast<float*>(workspace);
   float* scal = ws + p.off_scal;
-  if (B > 0)
+  char* sc = reinterpret_cast<char*>(scratch);
+  if (B > 0 && !det) {
     hipLaunchKernelGGL(hhfm_train_rows, dim3(grid_for_n(B * 64)), dim3(256), 0, st, X, Neg, B,
                        ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E, features_M, k,
                        ws + p.off_dE, scal);
+  } else if (B > 0) {
+    float* gb = reinterpret_cast<float*>(sc + d.g);
+    float* gtb = reinterpret_cast<float*>(sc + d.gt);
+    uint32_t* maskb = reinterpret_cast<uint32_t*>(sc + d.mask);
+    float* HV = reinterpret_cast<float*>(sc + d.rowvec);
+    hipLaunchKernelGGL(hhfm_train_rows_det, dim3(grid_for_n(B * 64)), dim3(256), 0, st, X, Neg, B,
+                       ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E, features_M, k, gb,
+                       gtb, maskb, reinterpret_cast<double*>(sc + d.loss), HV);
+    const OccSource src{X, Neg, ncols, NG, ctx_begin, ctx_begin + nc, time_begin, time_begin + nt};
+    const int rc = det_scatter(d, sc, src, S, B, features_M, E, k, ws + p.off_dE, nullptr, nullptr,
+                               scal, HhfmContrib{gb, gtb, maskb, HV, S, NG, k}, st);
+    if (rc != 0) return rc;
+  }
   // E's gradient is dense through λ·l2(E) (OurModel7.py:180-184), sparse at λ = 0
   const OptVar vars[] = {{E, ws + p.off_dE, accE, features_M * k, lam, k, lam == 0.f, true}};
   uint8_t* touched = reinterpret_cast<uint8_t*>(ws + p.off_touch);
   return optimizer_tail(vars, (int)std::size(vars), {{X, B * ncols}, {Neg, B * NG}}, features_M,
-                        optimizer, lr, scal, touched, lam, loss, st);
+                        optimizer, lr, scal, touched, lam, loss, st,
+                        det ? reinterpret_cast<float*>(sc + d.sspart) : nullptr);
+}
+
+extern "C" int hhfm_hhfm_train_step(const int32_t* X, const int32_t* Neg, int64_t B,
+                                    int32_t ncols, int32_t ctx_begin, int32_t ctx_end,
+                                    int32_t time_begin, int32_t time_end, int32_t NG, float* E,
+                                    int64_t features_M, int32_t k, float lr, float lam,
+                                    int32_t optimizer, float* accE, void* workspace,
+                                    size_t ws_bytes, float* loss, void* stream) {
+  return hhfm_train_step_impl(X, Neg, B, ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E,
+                              features_M, k, lr, lam, optimizer, accE, workspace, ws_bytes, false,
+                              nullptr, 0, loss, stream);
+}
+
+extern "C" int hhfm_hhfm_train_step_det(const int32_t* X, const int32_t* Neg, int64_t B,
+                                        int32_t ncols, int32_t ctx_begin, int32_t ctx_end,
+                                        int32_t time_begin, int32_t time_end, int32_t NG,
+                                        float* E, int64_t features_M, int32_t k, float lr,
+                                        float lam, int32_t optimizer, float* accE,
+                                        void* workspace, size_t ws_bytes, void* scratch,
+                                        size_t scratch_bytes, float* loss, void* stream) {
+  return hhfm_train_step_impl(X, Neg, B, ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E,
+                              features_M, k, lr, lam, optimizer, accE, workspace, ws_bytes, true,
+                              scratch, scratch_bytes, loss, stream);
 }
 
 extern "C" int hhfm_dfm_train_workspace(int64_t B, int32_t F, int32_t k, int64_t features_M,

@@ -115,6 +115,18 @@ def _next_seed(model, st):
     return seed
 
 
+def _det_scratch(model, st, B, occ_per_row):
+    """The deterministic steps' per-batch scratch (include/hhfm.h
+    hhfm_train_det_scratch), reallocated when a larger batch comes: it carries
+    no state, so there is nothing to copy or zero."""
+    if st.get("det") is None or st["det_rows"] < B:
+        M, k = model.weights["feature_embeddings"].shape
+        nbytes = native().train_det_scratch(B, occ_per_row, k, M)
+        st["det"] = torch.empty(nbytes, dtype=torch.uint8, device=model.device)
+        st["det_rows"] = B
+    return st["det"]
+
+
 def fm_partial_fit(model, data) -> float:
     """FM.partial_fit (FM.py:168-171): one optimizer step, returns the loss
     (of the dropped forward when keep < 1, FM.py:114)."""
@@ -126,13 +138,17 @@ def fm_partial_fit(model, data) -> float:
     y = _labels(model, data)
     B, F = X.shape
     M, k = W["feature_embeddings"].shape
-    native().fm_train_step_ex(X.data_ptr(), y.data_ptr(), B, F,
-                              W["feature_embeddings"].data_ptr(), W["feature_bias"].data_ptr(),
-                              W["bias"].data_ptr(), M, k, float(model.learning_rate),
-                              float(model.lamda_bilinear), opt, keep, _next_seed(model, st),
-                              st["feature_embeddings"].data_ptr(), st["feature_bias"].data_ptr(),
-                              st["bias"].data_ptr(), st["ws"].data_ptr(), st["ws"].numel(),
-                              st["loss"].data_ptr(), ops._stream(model.device))
+    args = (X.data_ptr(), y.data_ptr(), B, F, W["feature_embeddings"].data_ptr(),
+            W["feature_bias"].data_ptr(), W["bias"].data_ptr(), M, k, float(model.learning_rate),
+            float(model.lamda_bilinear), opt, keep, _next_seed(model, st),
+            st["feature_embeddings"].data_ptr(), st["feature_bias"].data_ptr(),
+            st["bias"].data_ptr(), st["ws"].data_ptr(), st["ws"].numel())
+    tail = (st["loss"].data_ptr(), ops._stream(model.device))
+    if getattr(model, "deterministic", False):
+        sc = _det_scratch(model, st, B, F)
+        native().fm_train_step_det(*args, sc.data_ptr(), sc.numel(), *tail)
+    else:
+        native().fm_train_step_ex(*args, *tail)
     return float(st["loss"].item())
 
 
@@ -152,12 +168,18 @@ def hhfm_partial_fit(model, data) -> float:
     B, ncols = X.shape
     ctx, tim = model._ranges(ncols)
     M, k = W["feature_embeddings"].shape
-    native().hhfm_train_step(X.data_ptr(), Neg.data_ptr(), B, ncols, ctx[0], ctx[1], tim[0],
-                             tim[1], Neg.shape[1], W["feature_embeddings"].data_ptr(), M, k,
-                             float(model.learning_rate), float(model.lamda_bilinear), opt,
-                             st["feature_embeddings"].data_ptr(), st["ws"].data_ptr(),
-                             st["ws"].numel(), st["loss"].data_ptr(),
-                             ops._stream(model.device))
+    NG = Neg.shape[1]
+    args = (X.data_ptr(), Neg.data_ptr(), B, ncols, ctx[0], ctx[1], tim[0], tim[1], NG,
+            W["feature_embeddings"].data_ptr(), M, k, float(model.learning_rate),
+            float(model.lamda_bilinear), opt, st["feature_embeddings"].data_ptr(),
+            st["ws"].data_ptr(), st["ws"].numel())
+    tail = (st["loss"].data_ptr(), ops._stream(model.device))
+    if getattr(model, "deterministic", False):
+        occ = 2 + NG + (ctx[1] - ctx[0]) + (tim[1] - tim[0])   # item, negatives, user, fields
+        sc = _det_scratch(model, st, B, occ)
+        native().hhfm_train_step_det(*args, sc.data_ptr(), sc.numel(), *tail)
+    else:
+        native().hhfm_train_step(*args, *tail)
     return float(st["loss"].item())
 
 

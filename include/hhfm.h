@@ -457,6 +457,64 @@ int hhfm_fm_train_step_ex(const int32_t* idx, const float* y, int64_t B, int32_t
 int hhfm_dropout_mask(uint64_t seed, int32_t site, int64_t rows, int32_t n, float keep,
                       float* binary, void* stream);
 
+/* Deterministic training steps (opt-in; FM and HHFM).  The steps above add
+ * their gradients with float atomics, whose order changes from run to run.
+ * hhfm_fm_train_step_det / hhfm_hhfm_train_step_det are hhfm_fm_train_step_ex /
+ * hhfm_hhfm_train_step with no float atomic: the order of every sum is a
+ * function of the batch alone.
+ *
+ * The contribution of one occurrence of an id in the batch is the value the
+ * default step adds atomically, formed from the same expressions in the same
+ * order (s = Σ_f E[x_f][c] in field order, g·(s − e), g·h, −gt·h,
+ * dh = g·it − gt·nsum); only the order in which contributions meet differs:
+ *   dE[id][c], dw[id]   the fp32 sum of the id's contributions in ascending
+ *       occurrence index o = b·S + slot, started from the first one.
+ *       FM: S = F, slot = the field.  HHFM: S = 2 + NG + ctx columns + time
+ *       columns, slots in the order item, negatives 0..NG-1, user, context
+ *       columns ascending, time columns ascending.  Only tied maxima
+ *       contribute (an untied negative adds nothing); a column that FM's
+ *       dropout drops adds nothing; ids are clamped to row 0 as always.
+ *   w0's gradient, the data loss   per-row values g_b (float) and loss_b
+ *       (double; FM r²/2 formed in double, HHFM −logf(σ) widened): 256
+ *       partials, partial t = rows t, t + 256, ... added in ascending order
+ *       from 0, then the 256 partials in ascending t from 0; the loss is
+ *       rounded to float once.
+ *   Σ var² of the l2 term   the optimizer's grid is a function of the
+ *       variable's size alone; every wave's partial is stored at its global
+ *       wave index and the partials are added in ascending index in double,
+ *       rounded to float once.
+ * Promised: with the same build, the same device model, the same inputs, the
+ * same initial parameters and slots and the same seed, the parameters, slots
+ * and *loss are the same bits — in the same process or a fresh one, on any
+ * stream.  NOT promised: equal bits to the default steps, to TensorFlow, or
+ * across builds.  (numpy restatement of the orders: tests/train_det_ref.py.)
+ *
+ * `scratch` holds hhfm_train_det_scratch(B, occ_per_row, k, features_M) bytes
+ * for batches of exactly that shape or any smaller B (occ_per_row = F for FM,
+ * the S above for HHFM): sort keys and values, hipCUB's temporary storage,
+ * the run starts, the per-row vectors and scalars, the Σvar² partials.  It
+ * carries no state between steps and need not be zeroed; the size query runs
+ * on the host and needs no device, and is HHFM_EINVAL when B·occ_per_row does
+ * not fit an int.  The workspace is the default steps' (hhfm_train_workspace),
+ * same layout, still left zeroed.  The default steps' argument checks come
+ * first, in their order; then a NULL or too small scratch is HHFM_EINVAL
+ * before anything is launched (also at B = 0, whose Σvar² partials live
+ * there). */
+int hhfm_train_det_scratch(int64_t B, int32_t occ_per_row, int32_t k, int64_t features_M,
+                           size_t* bytes);
+int hhfm_fm_train_step_det(const int32_t* idx, const float* y, int64_t B, int32_t F, float* E,
+                           float* w, float* w0, int64_t features_M, int32_t k, float lr,
+                           float lambda_l2, int32_t optimizer, float keep, uint64_t seed,
+                           float* accE, float* accw, float* accw0, void* workspace,
+                           size_t ws_bytes, void* scratch, size_t scratch_bytes, float* loss,
+                           void* stream);
+int hhfm_hhfm_train_step_det(const int32_t* X, const int32_t* Neg, int64_t B, int32_t ncols,
+                             int32_t ctx_begin, int32_t ctx_end, int32_t time_begin,
+                             int32_t time_end, int32_t NG, float* E, int64_t features_M,
+                             int32_t k, float lr, float lambda_l2, int32_t optimizer,
+                             float* accE, void* workspace, size_t ws_bytes, void* scratch,
+                             size_t scratch_bytes, float* loss, void* stream);
+
 /* DeepFM (DFM.py:139-155, 214-217; use_fm = use_deep = True, loss "mse"):
  *   loss = Σ (y − out)²/2 + λ·(‖Wp‖² + Σ_l ‖W_l‖²)/2
  * one step of the optimizer (codes as above) on every variable, in place.

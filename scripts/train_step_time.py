@@ -3,8 +3,11 @@ kernels) at the reference's default batch (5000 rows, Frappe shape, k = A = 64,
 Adagrad), with the native extension loaded from a given folder, so that two
 builds (say a commit's and its parent's) can be alternated, a fresh process
 each.  Prints one JSON line: per case the sorted µs / step of 7 windows of 40
-steps; --drop adds FM at keep 0.5 and AFM at keep [0.8, 0.5].
-usage: python scripts/train_step_time.py LIBDIR TAG [--drop]"""
+steps; --drop adds FM at keep 0.5 and AFM at keep [0.8, 0.5]; --det adds an HHFM
+step (NG = 10) and the deterministic steps (FM at keep 1 and 0.5, HHFM) next
+to their default ones, and FM at B = 32,773 with one id in every row (the
+longest serial walk of the segment pass), default and deterministic.
+usage: python scripts/train_step_time.py LIBDIR TAG [--drop] [--det]"""
 import importlib.machinery
 import importlib.util
 import json
@@ -17,6 +20,7 @@ import torch
 
 libdir, tag = sys.argv[1], sys.argv[2]
 drop = "--drop" in sys.argv
+det = "--det" in sys.argv
 ext = sysconfig.get_config_var("EXT_SUFFIX")
 path = os.path.join(os.path.abspath(libdir), "_hhfm" + ext)
 loader = importlib.machinery.ExtensionFileLoader("_hhfm", path)
@@ -101,5 +105,51 @@ res = {"tag": tag, "fm_keep1_us": timed(fm_plain), "afm_keep1_us": timed(afm_pla
 if drop:
     res["fm_keep0.5_us"] = timed(fm_drop)
     res["afm_keep0.8_0.5_us"] = timed(afm_drop)
+
+if det:
+    def scratch(rows, occ):
+        return torch.empty(nat.train_det_scratch(rows, occ, k, M), dtype=torch.uint8,
+                           device="cuda")
+
+    def fm_step(Xt, yt, rows, keep, sc):
+        """One FM step on Xt: the default path, or the deterministic one on scratch sc."""
+        def fn():
+            step[0] += 1
+            args = (Xt.data_ptr(), yt.data_ptr(), rows, F, *p, M, k, 0.1, 0.1, 0, keep,
+                    2016 | step[0] << 32, *a, ws.data_ptr(), ws.numel())
+            if sc is None:
+                nat.fm_train_step_ex(*args, loss.data_ptr(), st)
+            else:
+                nat.fm_train_step_det(*args, sc.data_ptr(), sc.numel(), loss.data_ptr(), st)
+        return fn
+
+    NG = 10
+    Neg = dev(rng.integers(nu, nu + ni, (B, NG)).astype(np.int32))
+    (hE,), (hacc,) = params([(M, k)], [0.1])
+    hws = torch.zeros(nat.train_workspace(M, k), dtype=torch.uint8, device="cuda")
+
+    def hhfm_step(sc):
+        def fn():
+            args = (X.data_ptr(), Neg.data_ptr(), B, F, 2, F, 0, 0, NG, hE.data_ptr(), M, k, 0.1,
+                    0.01, 0, hacc.data_ptr(), hws.data_ptr(), hws.numel())
+            if sc is None:
+                nat.hhfm_train_step(*args, loss.data_ptr(), st)
+            else:
+                nat.hhfm_train_step_det(*args, sc.data_ptr(), sc.numel(), loss.data_ptr(), st)
+        return fn
+
+    sc = scratch(B, F)
+    res["fm_det_keep1_us"] = timed(fm_step(X, y, B, 1.0, sc))
+    res["fm_det_keep0.5_us"] = timed(fm_step(X, y, B, 0.5, sc))
+    res["fm_keep0.5_us"] = timed(fm_step(X, y, B, 0.5, None))
+    res["hhfm_ng10_us"] = timed(hhfm_step(None))
+    res["hhfm_det_ng10_us"] = timed(hhfm_step(scratch(B, 2 + NG + F - 2)))
+    # one id in every row: its 32,773 occurrences are one wave's serial walk
+    Bh = 32773
+    Xh = rng.integers(0, M, (Bh, F)).astype(np.int32)
+    Xh[:, 0] = 0
+    Xh, yh = dev(Xh), dev(rng.choice([1.0, -1.0], Bh).astype(np.float32))
+    res["fm_hot32773_us"] = timed(fm_step(Xh, yh, Bh, 1.0, None), reps=3, n=10)
+    res["fm_det_hot32773_us"] = timed(fm_step(Xh, yh, Bh, 1.0, scratch(Bh, F)), reps=3, n=10)
 res = {k_: ([round(v, 2) for v in vs] if isinstance(vs, list) else vs) for k_, vs in res.items()}
 print(json.dumps(res))

@@ -39,6 +39,8 @@ def parse_args(dataname, factor, TopK, argv=None):
     p.add_argument("--TopK", type=int, default=TopK)
     p.add_argument("--Result", type=int, default=0)
     p.add_argument("--result_file", default="../result.txt")
+    p.add_argument("--deterministic", type=int, default=0,
+                   help="1: bit-reproducible training steps (row-ordered sums)")
     return p.parse_args(argv)
 
 
@@ -46,7 +48,8 @@ class AFM(ScoringModel):
     def __init__(self, n_user, n_item, features_M, attention, hidden_factor,
                  activation_function, learning_rate, lamda_attention, keep, optimizer_type,
                  decay, valid_dimension, random_seed=2016, device=None,
-                 table_dtype=torch.float32):
+                 table_dtype=torch.float32, deterministic=False):
+        self.deterministic = bool(deterministic)
         self.n_user = n_user
         self.n_item = n_item
         self.learning_rate = learning_rate
@@ -119,7 +122,8 @@ class AFM(ScoringModel):
         return super()._run_fetch(fetch, feed)
 
     def partial_fit(self, data):
-        """AFM.py:205-207 -> hhfm_afm_train_step (loss, then the update)."""
+        """AFM.py:205-207 -> hhfm_afm_train_step (loss, then the update);
+        hhfm_afm_train_step_det when ``deterministic``."""
         from .training import afm_partial_fit
         return afm_partial_fit(self, data)
 
@@ -140,7 +144,8 @@ class Train(harness.Train):
                      args.lamda_attention, args.keep, args.optimizer, args.batch_norm))
         self.model = model if model is not None else AFM(
             self.n_user, self.n_item, self.data.features_M, args.attention, hf, None, args.lr,
-            args.lamda_attention, keep, args.optimizer, args.decay, self.valid_dimension)
+            args.lamda_attention, keep, args.optimizer, args.decay, self.valid_dimension,
+            deterministic=bool(getattr(args, "deterministic", 0)))
 
     def train(self):
         from .training import run_training

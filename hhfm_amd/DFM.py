@@ -39,6 +39,8 @@ def parse_args(dataname, factor, Topk, argv=None):
     p.add_argument("--TopK", type=int, default=Topk)
     p.add_argument("--Result", type=int, default=0)
     p.add_argument("--result_file", default="../result.txt")
+    p.add_argument("--deterministic", type=int, default=0,
+                   help="1: bit-reproducible training steps (row-ordered sums)")
     return p.parse_args(argv)
 
 
@@ -46,7 +48,8 @@ class DeepFM(ScoringModel):
     def __init__(self, n_user, n_item, feature_size, field_size, embedding_size, deep_layers,
                  deep_layers_activation=None, learning_rate=0.01, verbose=True, l2_reg=0.0,
                  random_seed=2016, use_fm=True, use_deep=True, loss_type="mse", device=None,
-                 table_dtype=torch.float32, mlp_dtype=torch.float32):
+                 table_dtype=torch.float32, mlp_dtype=torch.float32, deterministic=False):
+        self.deterministic = bool(deterministic)
         assert use_fm or use_deep
         assert loss_type in ["logloss", "mse"], \
             "loss_type can be either 'logloss' for classification task or 'mse' for regression task"
@@ -165,7 +168,8 @@ class Train(harness.Train):
                      args.lamda, args.keep, args.optimizer, args.batch_norm))
         self.model = model if model is not None else DeepFM(
             self.n_user, self.n_item, self.data.features_M, self.data.Train_data.shape[1] - 1,
-            args.hidden_factor, [150, 200, 150], None, args.lr, args.verbose, args.lamda)
+            args.hidden_factor, [150, 200, 150], None, args.lr, args.verbose, args.lamda,
+            deterministic=bool(getattr(args, "deterministic", 0)))
 
     def train(self):
         from .training import run_training

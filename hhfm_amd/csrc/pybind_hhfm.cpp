@@ -580,6 +580,73 @@ PYBIND11_MODULE(_hhfm, m) {
           check(rc, "hhfm_afm_train_step_ex");
         });
 
+  // the deterministic AFM / DeepFM steps (include/hhfm.h)
+  m.def("afm_train_det_scratch", [](int64_t B, int F, int k, int A, int64_t M) {
+    size_t n = 0;
+    check(hhfm_afm_train_det_scratch(B, F, k, A, M, &n), "hhfm_afm_train_det_scratch");
+    return n;
+  });
+
+  m.def("dfm_train_det_scratch",
+        [](int64_t B, int F, int k, int64_t M, std::vector<int32_t> dims) {
+          size_t n = 0;
+          check(hhfm_dfm_train_det_scratch(B, F, k, M, (int)dims.size(), dims.data(), &n),
+                "hhfm_dfm_train_det_scratch");
+          return n;
+        });
+
+  m.def("afm_train_step_det",
+        [](uptr idx, uptr y, int64_t B, int F, uptr E, uptr w, uptr w0, int64_t M, int k, int A,
+           uptr W, uptr b, uptr pvec, uptr Pv, float lr, float lam, int opt, float keep_att,
+           float keep_afm, uint64_t seed, std::vector<uptr> acc, uptr ws, size_t ws_bytes,
+           uptr scratch, size_t scratch_bytes, uptr loss, uptr stream) {
+          if (opt != HHFM_OPT_SGD && acc.size() != 7)
+            throw py::value_error("acc needs 7 slot arrays (E, w, w0, W, b, pvec, P)");
+          std::vector<float*> av(acc.size());
+          for (size_t i = 0; i < acc.size(); ++i) av[i] = P<float>(acc[i]);
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_afm_train_step_det(P<const int32_t>(idx), P<const float>(y), B, F,
+                                         P<float>(E), P<float>(w), P<float>(w0), M, k, A,
+                                         P<float>(W), P<float>(b), P<float>(pvec), P<float>(Pv),
+                                         lr, lam, opt, keep_att, keep_afm, seed,
+                                         av.empty() ? nullptr : av.data(), P<void>(ws), ws_bytes,
+                                         P<void>(scratch), scratch_bytes, P<float>(loss),
+                                         P<void>(stream));
+          }
+          check(rc, "hhfm_afm_train_step_det");
+        });
+
+  m.def("dfm_train_step_det",
+        [](uptr idx, uptr y, int64_t B, int F, uptr E, uptr w, int64_t M, int k,
+           std::vector<int32_t> dims, std::vector<uptr> W, std::vector<uptr> bias, uptr Wp,
+           uptr bp, float lr, float lam, int opt, std::vector<uptr> acc, uptr ws,
+           size_t ws_bytes, uptr scratch, size_t scratch_bytes, uptr loss, uptr stream) {
+          if (W.size() != dims.size() || bias.size() != dims.size())
+            throw py::value_error("dims, W and bias must have the same length");
+          if (opt != HHFM_OPT_SGD && acc.size() != 2 * dims.size() + 4)
+            throw py::value_error("acc needs 2 * len(dims) + 4 slot arrays");
+          std::vector<float*> Wv(W.size()), bv(bias.size()), av(acc.size());
+          for (size_t i = 0; i < W.size(); ++i) {
+            Wv[i] = P<float>(W[i]);
+            bv[i] = P<float>(bias[i]);
+          }
+          for (size_t i = 0; i < acc.size(); ++i) av[i] = P<float>(acc[i]);
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_dfm_train_step_det(P<const int32_t>(idx), P<const float>(y), B, F,
+                                         P<float>(E), P<float>(w), M, k, (int)dims.size(),
+                                         dims.data(), Wv.data(), bv.data(), P<float>(Wp),
+                                         P<float>(bp), lr, lam, opt,
+                                         av.empty() ? nullptr : av.data(), P<void>(ws), ws_bytes,
+                                         P<void>(scratch), scratch_bytes, P<float>(loss),
+                                         P<void>(stream));
+          }
+          check(rc, "hhfm_dfm_train_step_det");
+        });
+
   m.def("topk_dense",
         [](uptr scores, int64_t B, int N, int64_t ld, int K, int base, uptr top_score,
            uptr top_idx, int plan, uptr stream) {

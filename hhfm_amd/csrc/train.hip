@@ -11,6 +11,9 @@
 //   hhfm_fm_train_step_ex / hhfm_afm_train_step_ex  the same with `--keep` < 1
 //                         (tf.nn.dropout, FM.py:114, AFM.py:126 / :134) on the
 //                         mask of dropout.h; hhfm_dropout_mask writes that mask
+//   hhfm_*_train_step_det the four steps without float atomics, every sum in a
+//                         fixed order ("Deterministic ... steps" below; AFM's and
+//                         DeepFM's reuse their default kernels under a DET flag)
 //
 // One wave per batch row computes the forward score(s) and scatters the
 // gradient of the row's loss into dense fp32 gradient buffers with float
@@ -455,8 +458,11 @@ static FmTrainPlan fm_train_plan(int64_t M, int k) {
 //                 occurrences in ascending o and adds their contributions in
 //                 fp32, lane = column; one plain store per element of dE / dw
 //   scalars       det_scalars (g and the loss), det_sumsq (Σvar²)
-// The contribution of an occurrence is a functor C (FmContrib, HhfmContrib);
-// another model's scatter plugs in there.
+// The contribution of an occurrence is a functor C (FmContrib, HhfmContrib;
+// StoredContrib for AFM and DeepFM, whose scatter kernels' DET instantiations
+// are the row pass of their table gradient and whose head kernels' DET
+// instantiations store per-row values that det_columns adds in the scalar
+// order).
 // ---------------------------------------------------------------------------
 static size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
 
@@ -470,11 +476,15 @@ static int det_key_bits(int64_t M) {
 struct DetPlan {
   int n, bits;   // occurrences B·S, key bits of the sort
   size_t keys_in, keys_out, vals_in, vals_out, runs, nruns, rowvec, g, gt, mask, loss, sspart,
-      tmp, tmp_bytes, bytes;
+      tmp, tmp_bytes, bias, heads, bytes;
 };
 
-static bool det_plan(int64_t B, int S, int k, int64_t M, DetPlan& p) {
-  if (B < 0 || S < 1 || k < 1 || M < 1) return false;
+// rowvec_f / ss_f: floats of the per-row (or per-occurrence) vectors and of
+// the Σvar² partials; bias_f / heads_f: the AFM / DeepFM steps' per-occurrence
+// dw values and per-row head values (0 for FM / HHFM).
+static bool det_plan_regions(int64_t B, int S, int64_t M, int64_t rowvec_f, int64_t ss_f,
+                             int64_t bias_f, int64_t heads_f, DetPlan& p) {
+  if (B < 0 || S < 1 || M < 1) return false;
   if (B > 0x7fffffff || B * S > 0x7fffffff) return false;   // the sort counts in int
   p = DetPlan{};
   p.n = (int)(B * S);
@@ -499,15 +509,23 @@ static bool det_plan(int64_t B, int S, int k, int64_t M, DetPlan& p) {
   p.vals_out = take((size_t)p.n * 4);
   p.runs = take((size_t)p.n * 4);
   p.nruns = take(4);
-  p.rowvec = take((size_t)B * 2 * k * 4);   // FM uses [B][k], HHFM [B][2k]
+  p.rowvec = take((size_t)rowvec_f * 4);
   p.g = take((size_t)B * 4);
   p.gt = take((size_t)B * 4);
   p.mask = take((size_t)B * 4);
   p.loss = take((size_t)B * 8);
-  p.sspart = take((size_t)det_sumsq_floats(M * k) * 4);
+  p.sspart = take((size_t)ss_f * 4);
   p.tmp = take(p.tmp_bytes);
+  p.bias = take((size_t)bias_f * 4);
+  p.heads = take((size_t)heads_f * 4);
   p.bytes = off;
   return true;
+}
+
+// FM / HHFM: the row vectors are FM's [B][k] or HHFM's [B][2k]; Σvar² over the table
+static bool det_plan(int64_t B, int S, int k, int64_t M, DetPlan& p) {
+  if (k < 1 || B < 0 || M < 1) return false;
+  return det_plan_regions(B, S, M, B * 2 * k, det_sumsq_floats(M * k), 0, 0, p);
 }
 
 // FM's row pass: fm_train_rows's forward (the same expressions in the same
@@ -753,6 +771,28 @@ struct HhfmContrib {
   }
 };
 
+// AFM's and DeepFM's, o = b·F + f: the det instantiation of the model's
+// scatter kernel stored what the default one hands to atomicAdd — V[o][c] for
+// dE and wb[o] for dw (AFM g_b, DeepFM g_b·Wp[f]) — so an occurrence's
+// contribution is one load, whatever the model.
+struct StoredContrib {
+  static constexpr bool kBias = true;
+  const float* V;    // [B·F][k]
+  const float* wb;   // [B·F]
+  int k;
+  struct Occ {
+    int o;
+    float wb;
+  };
+  HHFM_DEV Occ load(int o) const { return Occ{o, wb[o]}; }
+  HHFM_DEV Occ lane(const Occ& oc, int u) const { return Occ{lane_i(oc.o, u), lane_f(oc.wb, u)}; }
+  HHFM_DEV float bias(const Occ& oc) const { return oc.wb; }
+  HHFM_DEV bool value(const Occ& oc, int c, float, float& out) const {
+    out = V[(int64_t)oc.o * k + c];
+    return true;
+  }
+};
+
 // One wave per distinct id (grid-stride over the run list), lane = column
 // (strided for k > 64).  The id's occurrences lie consecutively in `vals`, in
 // ascending o.  The wave takes 64 at a time: lane u loads occurrence u's row
@@ -864,6 +904,38 @@ __global__ __launch_bounds__(256) void det_scalars(const float* __restrict__ gb,
     if (gb) scal[kScalBiasGrad] = A;
     scal[kScalDataLoss] = (float)D;
   }
+}
+
+// A dense head gradient in the scalar order: workgroup c adds column c of the
+// per-row values V [B][ld] as det_scalars adds g — thread t rows t, t + 256,
+// ... ascending from 0, thread 0 the 256 partials in ascending t from 0 —
+// and stores out[c] (plain store; the buffer was zero).
+__global__ __launch_bounds__(256) void det_columns(const float* __restrict__ V, int64_t B,
+                                                   int64_t ld, float* __restrict__ out) {
+  __shared__ float sv[256];
+  const int c = blockIdx.x;
+  float a = 0.f;
+  for (int64_t b = threadIdx.x; b < B; b += 256) a += V[b * ld + c];
+  sv[threadIdx.x] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float A = 0.f;
+    for (int t = 0; t < 256; ++t) A += sv[t];
+    out[c] = A;
+  }
+}
+
+// hipCUB's real temporary-storage figure against the plan's upper bound, before
+// a step launches anything (a refusal must leave the workspace untouched)
+static int det_sort_fits(const DetPlan& p, hipStream_t st) {
+  if (p.n == 0) return 0;
+  size_t tmp = 0;
+  uint32_t* kk = nullptr;
+  int32_t* vv = nullptr;
+  const hipError_t e =
+      hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, kk, kk, vv, vv, p.n, 0, p.bits, st);
+  if (e != hipSuccess) return (int)e;
+  return tmp > p.tmp_bytes ? HHFM_EWORKSPACE : 0;
 }
 
 // grouping + segment pass + scalars of one deterministic step (n > 0); the
@@ -999,12 +1071,17 @@ __global__ __launch_bounds__(256) void row_sums(const float* __restrict__ GT, in
 // Concat projection, forward and backward (DFM.py:109-137, l2_loss), wave
 // per row; each lane keeps its columns' dWp partials over the block's rows.
 // scal[kScalBiasGrad] += dbp  scal[kScalDataLoss] += (out − y)²/2
+// DET (hhfm_dfm_train_step_det): no atomics — the partials restart from zero at
+// every row and are stored per row (rowv [B][F+k+dL], for det_columns), the
+// row's loss goes to lossb in double, dw is left to the scatter pass.
+template <bool DET>
 __global__ __launch_bounds__(256) void dfm_train_head(
     const int32_t* __restrict__ idx, const float* __restrict__ y, int64_t B, int F,
     const float* __restrict__ E, const float* __restrict__ w, int64_t M, int k,
     const float* __restrict__ HL, int dL, int64_t ldh, const float* __restrict__ Wp,
     const float* __restrict__ bp, float* __restrict__ GL, float* __restrict__ gvec,
-    float* __restrict__ dWp, float* __restrict__ dw, float* __restrict__ scal) {
+    float* __restrict__ dWp, float* __restrict__ dw, float* __restrict__ scal,
+    float* __restrict__ rowv, double* __restrict__ lossb) {
   constexpr int NJ = kDfmHeadMaxCols / kWave;
   const int l = threadIdx.x & 63;
   const int D = F + k + dL;
@@ -1042,13 +1119,23 @@ __global__ __launch_bounds__(256) void dfm_train_head(
     }
     const float out = group_sum<kWave>(dot) + bp[0];
     const float g = out - y[m];                    // d l2_loss(y − out) / d out
-    sb += g;
-    sl += 0.5f * g * g;
+    if constexpr (DET) {
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) part[j] = 0.f;
+      if (l == 0) lossb[m] = 0.5 * ((double)g * (double)g);
+    } else {
+      sb += g;
+      sl += 0.5f * g * g;
+    }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int c = l + kWave * j;
       if (c < D) part[j] = fmaf(g, cv[j], part[j]);
-      if (c < F) atomicAdd(&dw[clamp_id(x[c], M)], g * Wp[c]);
+      if constexpr (DET) {
+        if (c < D) rowv[m * D + c] = part[j];
+      } else {
+        if (c < F) atomicAdd(&dw[clamp_id(x[c], M)], g * Wp[c]);
+      }
       if (c >= F + k && c < D) {
         const int n = c - F - k;
         GL[m * ldh + n] = cv[j] > 0.f ? g * Wp[c] : 0.f;   // relu' of the last layer
@@ -1056,6 +1143,7 @@ __global__ __launch_bounds__(256) void dfm_train_head(
     }
     if (l == 0) gvec[m] = g;
   }
+  if constexpr (DET) return;
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int c = l + kWave * j;
@@ -1068,16 +1156,22 @@ __global__ __launch_bounds__(256) void dfm_train_head(
 }
 
 // dE[x_f][c] += dX0[m][f·k + c] + g_m·Wp[F+c]·(Σ_f' e_f'c − e_fc)   (wave per row)
+// DET: the same value is stored at its occurrence instead, dE [B·F][k], and the
+// occurrence's dw value g_m·Wp[f] (the head's expression) in wb [B·F], for the
+// segment pass (StoredContrib).
+template <bool DET>
 __global__ __launch_bounds__(256) void dfm_train_scatter(
     const int32_t* __restrict__ idx, int64_t B, int F, const float* __restrict__ E, int64_t M,
     int k, const float* __restrict__ dX0, const float* __restrict__ gvec,
-    const float* __restrict__ Wp, float* __restrict__ dE) {
+    const float* __restrict__ Wp, float* __restrict__ dE, float* __restrict__ wb) {
   const int l = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
   const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
   for (int64_t m = wave; m < B; m += nwave) {
     const int32_t* x = idx + m * F;
     const float g = gvec[m];
+    if constexpr (DET)
+      for (int f = l; f < F; f += kWave) wb[m * F + f] = g * Wp[f];
     for (int c = l; c < k; c += kWave) {
       float s = 0.f;
       for (int f = 0; f < F; ++f) s += E[(int64_t)clamp_id(x[f], M) * k + c];
@@ -1085,7 +1179,11 @@ __global__ __launch_bounds__(256) void dfm_train_scatter(
       for (int f = 0; f < F; ++f) {
         const int64_t id = clamp_id(x[f], M);
         const float e = E[id * k + c];
-        atomicAdd(&dE[id * k + c], dX0[m * (int64_t)(F * k) + f * k + c] + gy2 * (s - e));
+        const float v = dX0[m * (int64_t)(F * k) + f * k + c] + gy2 * (s - e);
+        if constexpr (DET)
+          dE[(m * F + f) * k + c] = v;
+        else
+          atomicAdd(&dE[id * k + c], v);
       }
     }
   }
@@ -1194,7 +1292,11 @@ constexpr int kAfmSplitK = 512;                            // combos per dW spli
 //   dP_c = g·m2_c·Σ_p ã_p pr_pc
 // `att` receives ã for the scatter.  k <= 256 and np <= 120: one Philox block
 // per lane and site serves the lane's columns l + 64·kc and pairs l + 64·j.
-template <bool DROP>
+// DET (hhfm_afm_train_step_det): no atomics — accP / accV / accB restart from
+// zero at every row and are stored per row (rowv [B][k + 2A]: dP, dp, db, for
+// det_columns), the row's loss goes to lossb in double, dw is left to the
+// scatter pass.
+template <bool DROP, bool DET = false>
 __global__ __launch_bounds__(256) void afm_train_head(
     const int32_t* __restrict__ idx, const float* __restrict__ y, int64_t B, int F,
     const float* __restrict__ E, const float* __restrict__ w, const float* __restrict__ w0,
@@ -1202,7 +1304,8 @@ __global__ __launch_bounds__(256) void afm_train_head(
     const float* __restrict__ P, float* __restrict__ Gz, float* __restrict__ PT,
     float* __restrict__ GzT, int64_t Kp, float* __restrict__ att, float* __restrict__ gvec,
     float* __restrict__ dP, float* __restrict__ dpv, float* __restrict__ db,
-    float* __restrict__ dw, float* __restrict__ scal, DropoutArgs dr) {
+    float* __restrict__ dw, float* __restrict__ scal, DropoutArgs dr,
+    float* __restrict__ rowv, double* __restrict__ lossb) {
   constexpr int NC = kAfmTrainMaxKA / kWave;
   __shared__ float sp_all[4][kAfmTrainMaxNp], lg_all[4][kAfmTrainMaxNp];
   const int l = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -1281,8 +1384,14 @@ __global__ __launch_bounds__(256) void afm_train_head(
     fb = group_sum<kWave>(fb);
     const float out = (os + fb) + w0[0];
     const float g = out - y[m];                      // d l2_loss(y − out) / d out
-    sg += g;
-    sl += 0.5f * g * g;
+    if constexpr (DET) {
+#pragma unroll
+      for (int j = 0; j < NC; ++j) accP[j] = accV[j] = accB[j] = 0.f;
+      if (l == 0) lossb[m] = 0.5 * ((double)g * (double)g);
+    } else {
+      sg += g;
+      sl += 0.5f * g * g;
+    }
     // da_p = g·s_p, dlogit_p = a_p (da_p − Σ a·da)
     float t = 0.f;
     for (int p = l; p < np; p += kWave) {
@@ -1353,9 +1462,21 @@ __global__ __launch_bounds__(256) void afm_train_head(
           accP[kc] = fmaf(g, afm, accP[kc]);
       }
     }
-    for (int f = l; f < F; f += kWave) atomicAdd(&dw[clamp_id(x[f], M)], g);
+    if constexpr (DET) {
+      float* rv = rowv + m * (k + 2 * A);
+#pragma unroll
+      for (int j = 0; j < NC; ++j) {
+        const int c = l + kWave * j;
+        if (c < k) rv[c] = accP[j];
+        if (c < A) rv[k + c] = accV[j];
+        if (c < A) rv[k + A + c] = accB[j];
+      }
+    } else {
+      for (int f = l; f < F; f += kWave) atomicAdd(&dw[clamp_id(x[f], M)], g);
+    }
     __builtin_amdgcn_wave_barrier();   // sp / lg are rewritten by the next row
   }
+  if constexpr (DET) return;
 #pragma unroll
   for (int j = 0; j < NC; ++j) {
     const int c = l + kWave * j;
@@ -1372,12 +1493,14 @@ __global__ __launch_bounds__(256) void afm_train_head(
 // dE[x_f][c] += Σ_{pairs ∋ f} (DP + a_p·d·P_c) ⊙ e_other   (wave per row, lanes over k)
 // DROP: `att` holds ã and the AFM-path term is ã_p·d·P_c·m2_c, m2 regenerated
 // from the counter (site 2); the DP term is unchanged.
-template <bool DROP>
+// DET: de[f] is stored at its occurrence instead, dE [B·F][k], and the
+// occurrence's dw value g_m in wb [B·F], for the segment pass (StoredContrib).
+template <bool DROP, bool DET = false>
 __global__ __launch_bounds__(256) void afm_train_scatter(
     const int32_t* __restrict__ idx, int64_t B, int F, const float* __restrict__ E, int64_t M,
     int k, const float* __restrict__ DP, const float* __restrict__ att,
     const float* __restrict__ gvec, const float* __restrict__ P, float* __restrict__ dE,
-    DropoutArgs dr) {
+    DropoutArgs dr, float* __restrict__ wb) {
   const int l = threadIdx.x & 63;
   const int np = F * (F - 1) / 2;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
@@ -1386,6 +1509,8 @@ __global__ __launch_bounds__(256) void afm_train_scatter(
     const int32_t* x = idx + m * F;
     const int64_t c0 = m * np;
     const float g = gvec[m];
+    if constexpr (DET)
+      for (int f = l; f < F; f += kWave) wb[m * F + f] = g;
     [[maybe_unused]] LaneDropout ld;
     for (int c = l; c < k; c += kWave) {
       float ev[kAfmTrainMaxF], de[kAfmTrainMaxF];
@@ -1409,7 +1534,12 @@ __global__ __launch_bounds__(256) void afm_train_scatter(
           }
 #pragma unroll
       for (int f = 0; f < kAfmTrainMaxF; ++f)
-        if (f < F) atomicAdd(&dE[(int64_t)clamp_id(x[f], M) * k + c], de[f]);
+        if (f < F) {
+          if constexpr (DET)
+            dE[(m * F + f) * k + c] = de[f];
+          else
+            atomicAdd(&dE[(int64_t)clamp_id(x[f], M) * k + c], de[f]);
+        }
     }
   }
 }
@@ -1468,6 +1598,25 @@ static bool afm_train_plan(int64_t B, int F, int k, int A, int64_t M, AfmTrainPl
   p.off_g = p.take(B);
   p.off_part = p.take((int64_t)p.S * k * A);
   return true;
+}
+
+// The scratch of the deterministic DeepFM / AFM steps: the grouping's regions
+// as for FM (S = F), the stored contributions [B·F][k] in `rowvec`, the
+// occurrences' dw values [B·F] in `bias`, the per-row head values in `heads`
+// (DeepFM [B][F+k+d_L]; AFM [B][k+2A]), the row losses, and one Σvar² partial
+// per wave of every λ-carrying variable's optimizer grid.
+static bool dfm_det_plan(int64_t B, int F, int k, int64_t M, const DfmTrainPlan& p, DetPlan& d) {
+  if (B > 0x7fffffff) return false;
+  const int D = F + k + p.d[p.L];
+  int64_t ss = det_sumsq_floats(D);
+  for (int i = 0; i < p.L; ++i) ss += det_sumsq_floats((int64_t)p.d[i] * p.d[i + 1]);
+  return det_plan_regions(B, F, M, B * F * k, ss, B * F, B * D, d);
+}
+
+static bool afm_det_plan(int64_t B, int F, int k, int A, int64_t M, DetPlan& d) {
+  if (B > 0x7fffffff) return false;
+  return det_plan_regions(B, F, M, B * F * k, det_sumsq_floats((int64_t)k * A), B * F,
+                          B * (k + 2 * A), d);
 }
 
 // tr_pad over src [R][C] (row stride lds): dst [C][ldd], rows R..Rp zero
@@ -1714,16 +1863,20 @@ extern "C" int hhfm_dfm_train_state_bytes(int32_t F, int32_t k, int64_t features
   return HHFM_OK;
 }
 
-extern "C" int hhfm_dfm_train_step(const int32_t* idx, const float* y, int64_t B, int32_t F,
-                                   float* E, float* w, int64_t features_M, int32_t k,
-                                   int32_t nlayers, const int32_t* layer_dims, float* const* W,
-                                   float* const* bias, float* Wp, float* bp, float lr,
-                                   float lambda_l2, int32_t optimizer, float* const* acc,
-                                   void* workspace, size_t ws_bytes, float* loss,
-                                   void* stream) {
+// The DeepFM step: the default path (det false; scratch unused), or the
+// deterministic one on `scratch` (hhfm_dfm_train_det_scratch bytes).
+static int dfm_train_step_impl(const int32_t* idx, const float* y, int64_t B, int32_t F, float* E,
+                               float* w, int64_t features_M, int32_t k, int32_t nlayers,
+                               const int32_t* layer_dims, float* const* W, float* const* bias,
+                               float* Wp, float* bp, float lr, float lambda_l2,
+                               int32_t optimizer, float* const* acc, void* workspace,
+                               size_t ws_bytes, bool det, void* scratch, size_t scratch_bytes,
+                               float* loss, void* stream) {
   DfmTrainPlan p;
+  DetPlan d{};
   if (B < 0 || features_M < 1 || !layer_dims ||
-      !dfm_train_plan(B, F, k, features_M, nlayers, layer_dims, p))
+      !dfm_train_plan(B, F, k, features_M, nlayers, layer_dims, p) ||
+      (det && !dfm_det_plan(B, F, k, features_M, p, d)))
     return HHFM_EINVAL;
   if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
   if (!E || !w || !W || !bias || !Wp || !bp || !loss || !workspace) return HHFM_EINVAL;
@@ -1735,10 +1888,17 @@ extern "C" int hhfm_dfm_train_step(const int32_t* idx, const float* y, int64_t B
   if (!slots_ok(optimizer, acc, 2 * L + 4)) return HHFM_EINVAL;
   if (ws_bytes < (size_t)p.total * 4) return HHFM_EWORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (det) {
+    if (!scratch) return HHFM_EINVAL;
+    if (scratch_bytes < d.bytes) return HHFM_EWORKSPACE;
+    if (const int rc = det_sort_fits(d, st)) return rc;
+  }
   float* ws = reinterpret_cast<float*>(workspace);
   auto at = [&](int64_t off) { return ws + off; };
   float* scal = at(p.off_scal);
   const int64_t Bp = p.Bp;
+  char* sc = reinterpret_cast<char*>(scratch);
+  auto sf = [&](size_t off) { return reinterpret_cast<float*>(sc + off); };
 
   if (B > 0) {
     // weights: Wᵀ zero-padded (forward Bt) and W zero-padded (backward Bt)
@@ -1767,9 +1927,17 @@ extern "C" int hhfm_dfm_train_step(const int32_t* idx, const float* y, int64_t B
     // head: out, d = out − y, dWp, dbp, dw, last layer's delta
     const int64_t ldL = pad8(p.d[L]);
     (void)hipMemsetAsync(at(p.off_G[L]), 0, (size_t)(B * ldL) * 4, st);
-    hipLaunchKernelGGL(dfm_train_head, dim3(grid_for_n(B * 64 / 8)), dim3(256), 0, st, idx, y, B,
-                       F, E, w, features_M, k, at(p.off_H[L]), p.d[L], ldL, Wp, bp, at(p.off_G[L]),
-                       at(p.off_g), at(p.off_dWp), at(p.off_dw), scal);
+    hipLaunchKernelGGL(det ? dfm_train_head<true> : dfm_train_head<false>,
+                       dim3(grid_for_n(B * 64 / 8)), dim3(256), 0, st, idx, y, B, F, E, w,
+                       features_M, k, at(p.off_H[L]), p.d[L], ldL, Wp, bp, at(p.off_G[L]),
+                       at(p.off_g), at(p.off_dWp), at(p.off_dw), scal,
+                       det ? sf(d.heads) : nullptr,
+                       det ? reinterpret_cast<double*>(sc + d.loss) : nullptr);
+    if (det) {
+      const int D = F + k + p.d[L];
+      hipLaunchKernelGGL(det_columns, dim3(D), dim3(256), 0, st, sf(d.heads), B, (int64_t)D,
+                         at(p.off_dWp));
+    }
     launch_tr_pad(at(p.off_G[L]), B, p.d[L], ldL, nullptr, 0, at(p.off_GT[L]), Bp, Bp, st);
     // backward through the layers
     for (int i = L - 1; i >= 0; --i) {
@@ -1795,8 +1963,19 @@ extern "C" int hhfm_dfm_train_step(const int32_t* idx, const float* y, int64_t B
         launch_tr_pad(at(p.off_G[i]), B, din, pad8(din), at(p.off_H[i]), pad8(din),
                       at(p.off_GT[i]), Bp, Bp, st);
     }
-    hipLaunchKernelGGL(dfm_train_scatter, dim3(grid_for_n(B * 64)), dim3(256), 0, st, idx, B, F,
-                       E, features_M, k, at(p.off_dX0), at(p.off_g), Wp, at(p.off_dE));
+    if (!det) {
+      hipLaunchKernelGGL(dfm_train_scatter<false>, dim3(grid_for_n(B * 64)), dim3(256), 0, st,
+                         idx, B, F, E, features_M, k, at(p.off_dX0), at(p.off_g), Wp,
+                         at(p.off_dE), nullptr);
+    } else {
+      hipLaunchKernelGGL(dfm_train_scatter<true>, dim3(grid_for_n(B * 64)), dim3(256), 0, st, idx,
+                         B, F, E, features_M, k, at(p.off_dX0), at(p.off_g), Wp, sf(d.rowvec),
+                         sf(d.bias));
+      const OccSource src{idx, nullptr, F, 0, 0, 0, 0, 0};
+      const int rc = det_scatter(d, sc, src, F, B, features_M, E, k, at(p.off_dE), at(p.off_dw),
+                                 at(p.off_g), scal, StoredContrib{sf(d.rowvec), sf(d.bias), k}, st);
+      if (rc != 0) return rc;
+    }
   }
   // optimizer: λ only on the layer weights and the concat projection
   // (DFM.py:146-152); the table and w have IndexedSlices gradients (sparse)
@@ -1821,7 +2000,45 @@ extern "C" int hhfm_dfm_train_step(const int32_t* idx, const float* y, int64_t B
                 false};
   uint8_t* touched = reinterpret_cast<uint8_t*>(at(p.off_touch));
   return optimizer_tail(vars, nv, {{idx, B * F}}, features_M, optimizer, lr, scal, touched,
-                        lambda_l2, loss, st);
+                        lambda_l2, loss, st, det ? sf(d.sspart) : nullptr);
+}
+
+extern "C" int hhfm_dfm_train_step(const int32_t* idx, const float* y, int64_t B, int32_t F,
+                                   float* E, float* w, int64_t features_M, int32_t k,
+                                   int32_t nlayers, const int32_t* layer_dims, float* const* W,
+                                   float* const* bias, float* Wp, float* bp, float lr,
+                                   float lambda_l2, int32_t optimizer, float* const* acc,
+                                   void* workspace, size_t ws_bytes, float* loss,
+                                   void* stream) {
+  return dfm_train_step_impl(idx, y, B, F, E, w, features_M, k, nlayers, layer_dims, W, bias, Wp,
+                             bp, lr, lambda_l2, optimizer, acc, workspace, ws_bytes, false,
+                             nullptr, 0, loss, stream);
+}
+
+extern "C" int hhfm_dfm_train_step_det(const int32_t* idx, const float* y, int64_t B, int32_t F,
+                                       float* E, float* w, int64_t features_M, int32_t k,
+                                       int32_t nlayers, const int32_t* layer_dims,
+                                       float* const* W, float* const* bias, float* Wp, float* bp,
+                                       float lr, float lambda_l2, int32_t optimizer,
+                                       float* const* acc, void* workspace, size_t ws_bytes,
+                                       void* scratch, size_t scratch_bytes, float* loss,
+                                       void* stream) {
+  return dfm_train_step_impl(idx, y, B, F, E, w, features_M, k, nlayers, layer_dims, W, bias, Wp,
+                             bp, lr, lambda_l2, optimizer, acc, workspace, ws_bytes, true, scratch,
+                             scratch_bytes, loss, stream);
+}
+
+extern "C" int hhfm_dfm_train_det_scratch(int64_t B, int32_t F, int32_t k, int64_t features_M,
+                                          int32_t nlayers, const int32_t* layer_dims,
+                                          size_t* bytes) {
+  DfmTrainPlan p;
+  DetPlan d;
+  if (!bytes || !layer_dims || B < 0 || features_M < 1 ||
+      !dfm_train_plan(B, F, k, features_M, nlayers, layer_dims, p) ||
+      !dfm_det_plan(B, F, k, features_M, p, d))
+    return HHFM_EINVAL;
+  *bytes = d.bytes;
+  return HHFM_OK;
 }
 
 extern "C" int hhfm_afm_train_workspace(int64_t B, int32_t F, int32_t k, int32_t A,
@@ -1852,15 +2069,19 @@ extern "C" int hhfm_afm_train_step(const int32_t* idx, const float* y, int64_t B
                                 loss, stream);
 }
 
-extern "C" int hhfm_afm_train_step_ex(const int32_t* idx, const float* y, int64_t B, int32_t F,
-                                      float* E, float* w, float* w0, int64_t features_M,
-                                      int32_t k, int32_t A, float* W, float* b, float* pvec,
-                                      float* P, float lr, float lambda_att, int32_t optimizer,
-                                      float keep_att, float keep_afm, uint64_t seed,
-                                      float* const* acc, void* workspace, size_t ws_bytes,
-                                      float* loss, void* stream) {
+// The AFM step: the default path (det false; scratch unused), or the
+// deterministic one on `scratch` (hhfm_afm_train_det_scratch bytes).
+static int afm_train_step_impl(const int32_t* idx, const float* y, int64_t B, int32_t F, float* E,
+                               float* w, float* w0, int64_t features_M, int32_t k, int32_t A,
+                               float* W, float* b, float* pvec, float* P, float lr,
+                               float lambda_att, int32_t optimizer, float keep_att,
+                               float keep_afm, uint64_t seed, float* const* acc, void* workspace,
+                               size_t ws_bytes, bool det, void* scratch, size_t scratch_bytes,
+                               float* loss, void* stream) {
   AfmTrainPlan p;
-  if (!afm_train_plan(B, F, k, A, features_M, p) || !keep_ok(keep_att) || !keep_ok(keep_afm))
+  DetPlan d{};
+  if (!afm_train_plan(B, F, k, A, features_M, p) || !keep_ok(keep_att) || !keep_ok(keep_afm) ||
+      (det && !afm_det_plan(B, F, k, A, features_M, d)))
     return HHFM_EINVAL;
   const bool drop = keep_att < 1.f || keep_afm < 1.f;
   const DropoutArgs dr = dropout_args(keep_att, keep_afm, seed);
@@ -1870,6 +2091,13 @@ extern "C" int hhfm_afm_train_step_ex(const int32_t* idx, const float* y, int64_
   if (!slots_ok(optimizer, acc, 7)) return HHFM_EINVAL;   // acc: E, w, w0, W, b, pvec, P
   if (ws_bytes < (size_t)p.total * 4) return HHFM_EWORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (det) {
+    if (!scratch) return HHFM_EINVAL;
+    if (scratch_bytes < d.bytes) return HHFM_EWORKSPACE;
+    if (const int rc = det_sort_fits(d, st)) return rc;
+  }
+  char* sc = reinterpret_cast<char*>(scratch);
+  auto sf = [&](size_t off) { return reinterpret_cast<float*>(sc + off); };
   float* ws = reinterpret_cast<float*>(workspace);
   auto at = [&](int64_t off) { return ws + off; };
   float* scal = at(p.off_scal);
@@ -1894,10 +2122,22 @@ extern "C" int hhfm_afm_train_step_ex(const int32_t* idx, const float* y, int64_
     }
     // a few rows per wave: the per-wave dP / dp / db flush is k + 2A same-address atomics
     const unsigned hb = (unsigned)std::min<int64_t>(256, (B + 3) / 4);
-    hipLaunchKernelGGL(drop ? afm_train_head<true> : afm_train_head<false>, dim3(hb), dim3(256),
-                       0, st, idx, y, B, F, E, w, w0, features_M, k, A, at(p.off_R), pvec, P,
-                       at(p.off_Gz), PT, GzT, p.Kp, at(p.off_att), at(p.off_g), at(p.off_dP),
-                       at(p.off_dpv), at(p.off_db), at(p.off_dw), scal, dr);
+    auto head = det ? (drop ? afm_train_head<true, true> : afm_train_head<false, true>)
+                    : (drop ? afm_train_head<true> : afm_train_head<false>);
+    hipLaunchKernelGGL(head, dim3(hb), dim3(256), 0, st, idx, y, B, F, E, w, w0, features_M, k, A,
+                       at(p.off_R), pvec, P, at(p.off_Gz), PT, GzT, p.Kp, at(p.off_att),
+                       at(p.off_g), at(p.off_dP), at(p.off_dpv), at(p.off_db), at(p.off_dw), scal,
+                       dr, det ? sf(d.heads) : nullptr,
+                       det ? reinterpret_cast<double*>(sc + d.loss) : nullptr);
+    if (det) {   // row values [B][k + 2A]: dP, then dp, then db
+      const int64_t ld = k + 2 * A;
+      hipLaunchKernelGGL(det_columns, dim3(k), dim3(256), 0, st, sf(d.heads), B, ld,
+                         at(p.off_dP));
+      hipLaunchKernelGGL(det_columns, dim3(A), dim3(256), 0, st, sf(d.heads) + k, B, ld,
+                         at(p.off_dpv));
+      hipLaunchKernelGGL(det_columns, dim3(A), dim3(256), 0, st, sf(d.heads) + k + A, B, ld,
+                         at(p.off_db));
+    }
     if (p.Kp > p.n)
       hipLaunchKernelGGL(zero_cols, dim3(grid_for_n((int64_t)(k + A) * (p.Kp - p.n))),
                          dim3(256), 0, st, PT, k + A, p.Kp, p.n);
@@ -1911,9 +2151,20 @@ extern "C" int hhfm_afm_train_step_ex(const int32_t* idx, const float* y, int64_
       hipLaunchKernelGGL(sum_splits, dim3(grid_for_n((int64_t)k * A)), dim3(256), 0, st,
                          (const float*)at(p.off_part), p.S, (int64_t)k * A, at(p.off_dW));
     }
-    hipLaunchKernelGGL(drop ? afm_train_scatter<true> : afm_train_scatter<false>,
-                       dim3(grid_for_n(B * 64)), dim3(256), 0, st, idx, B, F, E, features_M, k,
-                       at(p.off_DP), at(p.off_att), at(p.off_g), P, at(p.off_dE), dr);
+    if (!det) {
+      hipLaunchKernelGGL(drop ? afm_train_scatter<true> : afm_train_scatter<false>,
+                         dim3(grid_for_n(B * 64)), dim3(256), 0, st, idx, B, F, E, features_M, k,
+                         at(p.off_DP), at(p.off_att), at(p.off_g), P, at(p.off_dE), dr, nullptr);
+    } else {
+      auto scat = drop ? afm_train_scatter<true, true> : afm_train_scatter<false, true>;
+      hipLaunchKernelGGL(scat, dim3(grid_for_n(B * 64)), dim3(256), 0, st, idx, B, F, E, features_M, k,
+                         at(p.off_DP), at(p.off_att), at(p.off_g), P, sf(d.rowvec), dr,
+                         sf(d.bias));
+      const OccSource src{idx, nullptr, F, 0, 0, 0, 0, 0};
+      const int rc = det_scatter(d, sc, src, F, B, features_M, E, k, at(p.off_dE), at(p.off_dw),
+                                 at(p.off_g), scal, StoredContrib{sf(d.rowvec), sf(d.bias), k}, st);
+      if (rc != 0) return rc;
+    }
   }
   // the table and w have IndexedSlices gradients (sparse); l2_regularizer(λ)
   // on attention_W only (AFM.py:146)
@@ -1928,6 +2179,42 @@ extern "C" int hhfm_afm_train_step_ex(const int32_t* idx, const float* y, int64_
       {P, at(p.off_dP), slot(6), k, 0.f, 1, false, false}};
   uint8_t* touched = reinterpret_cast<uint8_t*>(at(p.off_touch));
   return optimizer_tail(vars, (int)std::size(vars), {{idx, B * F}}, features_M, optimizer, lr,
-                        scal, touched, lambda_att, loss, st);
+                        scal, touched, lambda_att, loss, st, det ? sf(d.sspart) : nullptr);
+}
+
+extern "C" int hhfm_afm_train_step_ex(const int32_t* idx, const float* y, int64_t B, int32_t F,
+                                      float* E, float* w, float* w0, int64_t features_M,
+                                      int32_t k, int32_t A, float* W, float* b, float* pvec,
+                                      float* P, float lr, float lambda_att, int32_t optimizer,
+                                      float keep_att, float keep_afm, uint64_t seed,
+                                      float* const* acc, void* workspace, size_t ws_bytes,
+                                      float* loss, void* stream) {
+  return afm_train_step_impl(idx, y, B, F, E, w, w0, features_M, k, A, W, b, pvec, P, lr,
+                             lambda_att, optimizer, keep_att, keep_afm, seed, acc, workspace,
+                             ws_bytes, false, nullptr, 0, loss, stream);
+}
+
+extern "C" int hhfm_afm_train_step_det(const int32_t* idx, const float* y, int64_t B, int32_t F,
+                                       float* E, float* w, float* w0, int64_t features_M,
+                                       int32_t k, int32_t A, float* W, float* b, float* pvec,
+                                       float* P, float lr, float lambda_att, int32_t optimizer,
+                                       float keep_att, float keep_afm, uint64_t seed,
+                                       float* const* acc, void* workspace, size_t ws_bytes,
+                                       void* scratch, size_t scratch_bytes, float* loss,
+                                       void* stream) {
+  return afm_train_step_impl(idx, y, B, F, E, w, w0, features_M, k, A, W, b, pvec, P, lr,
+                             lambda_att, optimizer, keep_att, keep_afm, seed, acc, workspace,
+                             ws_bytes, true, scratch, scratch_bytes, loss, stream);
+}
+
+extern "C" int hhfm_afm_train_det_scratch(int64_t B, int32_t F, int32_t k, int32_t A,
+                                          int64_t features_M, size_t* bytes) {
+  AfmTrainPlan p;
+  DetPlan d;
+  if (!bytes || !afm_train_plan(B, F, k, A, features_M, p) ||
+      !afm_det_plan(B, F, k, A, features_M, d))
+    return HHFM_EINVAL;
+  *bytes = d.bytes;
+  return HHFM_OK;
 }
 

@@ -115,13 +115,14 @@ def _next_seed(model, st):
     return seed
 
 
-def _det_scratch(model, st, B, occ_per_row):
+def _det_scratch(model, st, B, occ_per_row=None, size_fn=None):
     """The deterministic steps' per-batch scratch (include/hhfm.h
-    hhfm_train_det_scratch), reallocated when a larger batch comes: it carries
-    no state, so there is nothing to copy or zero."""
+    hhfm_train_det_scratch, or ``size_fn(B)`` bytes for AFM / DeepFM),
+    reallocated when a larger batch comes: it carries no state, so there is
+    nothing to copy or zero."""
     if st.get("det") is None or st["det_rows"] < B:
         M, k = model.weights["feature_embeddings"].shape
-        nbytes = native().train_det_scratch(B, occ_per_row, k, M)
+        nbytes = size_fn(B) if size_fn else native().train_det_scratch(B, occ_per_row, k, M)
         st["det"] = torch.empty(nbytes, dtype=torch.uint8, device=model.device)
         st["det_rows"] = B
     return st["det"]
@@ -201,12 +202,18 @@ def dfm_partial_fit(model, data) -> float:
     ws = _ensure_ws(st, B, model.device, lambda b: nat.dfm_train_workspace(b, F, k, M, dims),
                     lambda: nat.dfm_train_state_bytes(F, k, M, dims))
     ptr = lambda n: W[n].data_ptr()  # noqa: E731
-    nat.dfm_train_step(X.data_ptr(), y.data_ptr(), B, F, ptr("feature_embeddings"),
-                       ptr("feature_bias"), M, k, dims, [ptr(f"layer_{i}") for i in range(L)],
-                       [ptr(f"bias_{i}") for i in range(L)], ptr("concat_projection"),
-                       ptr("concat_bias"), float(model.learning_rate), float(model.l2_reg),
-                       _ADAGRAD, [st[n].data_ptr() for n in names], ws.data_ptr(), ws.numel(),
-                       st["loss"].data_ptr(), ops._stream(model.device))
+    args = (X.data_ptr(), y.data_ptr(), B, F, ptr("feature_embeddings"), ptr("feature_bias"), M,
+            k, dims, [ptr(f"layer_{i}") for i in range(L)], [ptr(f"bias_{i}") for i in range(L)],
+            ptr("concat_projection"), ptr("concat_bias"), float(model.learning_rate),
+            float(model.l2_reg), _ADAGRAD, [st[n].data_ptr() for n in names], ws.data_ptr(),
+            ws.numel())
+    tail = (st["loss"].data_ptr(), ops._stream(model.device))
+    if getattr(model, "deterministic", False):
+        sc = _det_scratch(model, st, B,
+                          size_fn=lambda b: nat.dfm_train_det_scratch(b, F, k, M, dims))
+        nat.dfm_train_step_det(*args, sc.data_ptr(), sc.numel(), *tail)
+    else:
+        nat.dfm_train_step(*args, *tail)
     model._prep = None   # the scoring path's prepared (transposed / bf16) weights are stale
     return float(st["loss"].item())
 
@@ -231,14 +238,18 @@ def afm_partial_fit(model, data) -> float:
                     lambda: nat.afm_train_state_bytes(F, k, A, M))
     lam = float(model.lamda_attention) if model.lamda_attention > 0 else 0.0
     ptr = lambda n: W[n].data_ptr()  # noqa: E731
-    nat.afm_train_step_ex(X.data_ptr(), y.data_ptr(), B, F, ptr("feature_embeddings"),
-                          ptr("feature_bias"), ptr("bias"), M, k, A, ptr("attention_W"),
-                          ptr("attention_b"), ptr("attention_p"), ptr("prediction"),
-                          float(model.learning_rate), lam, opt, keep_att, keep_afm,
-                          _next_seed(model, st),
-                          [st[n].data_ptr() for n in names] if opt != _SGD else [],
-                          ws.data_ptr(), ws.numel(), st["loss"].data_ptr(),
-                          ops._stream(model.device))
+    args = (X.data_ptr(), y.data_ptr(), B, F, ptr("feature_embeddings"), ptr("feature_bias"),
+            ptr("bias"), M, k, A, ptr("attention_W"), ptr("attention_b"), ptr("attention_p"),
+            ptr("prediction"), float(model.learning_rate), lam, opt, keep_att, keep_afm,
+            _next_seed(model, st), [st[n].data_ptr() for n in names] if opt != _SGD else [],
+            ws.data_ptr(), ws.numel())
+    tail = (st["loss"].data_ptr(), ops._stream(model.device))
+    if getattr(model, "deterministic", False):
+        sc = _det_scratch(model, st, B,
+                          size_fn=lambda b: nat.afm_train_det_scratch(b, F, k, A, M))
+        nat.afm_train_step_det(*args, sc.data_ptr(), sc.numel(), *tail)
+    else:
+        nat.afm_train_step_ex(*args, *tail)
     return float(st["loss"].item())
 
 

@@ -457,7 +457,8 @@ int hhfm_fm_train_step_ex(const int32_t* idx, const float* y, int64_t B, int32_t
 int hhfm_dropout_mask(uint64_t seed, int32_t site, int64_t rows, int32_t n, float keep,
                       float* binary, void* stream);
 
-/* Deterministic training steps (opt-in; FM and HHFM).  The steps above add
+/* Deterministic training steps (opt-in; FM and HHFM here, AFM and DeepFM
+ * after their default steps below).  The steps above add
  * their gradients with float atomics, whose order changes from run to run.
  * hhfm_fm_train_step_det / hhfm_hhfm_train_step_det are hhfm_fm_train_step_ex /
  * hhfm_hhfm_train_step with no float atomic: the order of every sum is a
@@ -574,6 +575,63 @@ int hhfm_afm_train_step_ex(const int32_t* idx, const float* y, int64_t B, int32_
                            float lambda_att, int32_t optimizer, float keep_att, float keep_afm,
                            uint64_t seed, float* const* acc, void* workspace, size_t ws_bytes,
                            float* loss, void* stream);
+
+/* Deterministic AFM and DeepFM steps (opt-in), under the promise of
+ * "Deterministic training steps" above: hhfm_afm_train_step_det is
+ * hhfm_afm_train_step_ex (dropout included: the masks are a function of
+ * (seed, row, element)) and hhfm_dfm_train_step_det is hhfm_dfm_train_step,
+ * with no float atomic.  The GEMMs, AFM's split-order dW and DeepFM's db were
+ * order-fixed already; what changes is where contributions meet:
+ *   dE[id][c], dw[id]   an occurrence is o = b·F + f (FM's order).  Its
+ *       contribution to dE[id][c] is the value the default step hands to its
+ *       atomic add, from the same expressions in the same order — AFM:
+ *       de[f] = Σ_{pairs ∋ f} fma(fma(ã_p, g·P_c(·m2_c), DP[p][c]), e_other, ·)
+ *       in pair order i < j; DeepFM: dX0[b][f·k+c] + (g·Wp[F+c])·(s − e) — and
+ *       to dw[id] it is g_b (AFM) or g_b·Wp[f] (DeepFM).  Each is the fp32 sum
+ *       of the id's contributions in ascending o, started from the first one.
+ *       A dropped AFM column still contributes its DP term.
+ *   AFM dP[k], dp[A], db[A]; DeepFM dWp[F+k+d_L]   a row's value for an element
+ *       is what the default kernel's accumulator holds after that row alone,
+ *       from zero (the same fmaf chain over the row's pairs / columns).  The
+ *       element is the sum of the rows' values in the scalar order above: 256
+ *       partials, partial t = rows t, t + 256, ... ascending from 0, then the
+ *       partials in ascending t from 0, all in fp32.  The head kernel's grid
+ *       does not enter.
+ *   w0's / bp's gradient, the data loss   the scalar order above on g_b
+ *       (float) and g_b²/2 formed in double, rounded to float once.
+ *   Σ var²   as above, over attention_W (AFM) or every layer weight and the
+ *       concat projection in the optimizer's variable order W_0.., Wp (DeepFM).
+ * (numpy restatement: tests/train_det_heads_ref.py.)
+ *
+ * `scratch` holds hhfm_afm_train_det_scratch / hhfm_dfm_train_det_scratch
+ * bytes for batches of that shape or any smaller B: the grouping's regions as
+ * for FM, the stored contributions [B·F][k], the per-row head values, the
+ * row losses and the Σvar² partials.  It carries no state and need not be
+ * zeroed.  The size queries run on the host, need no device, and are
+ * HHFM_EINVAL wherever the matching workspace query is, or when B·F does not
+ * fit an int.  hipCUB's temporary storage is reserved by an upper bound; the
+ * step checks the real figure before it launches anything.  Workspaces are
+ * the default steps', same layout, still left zeroed.  The default steps'
+ * argument checks come first, in their order; then a NULL scratch is
+ * HHFM_EINVAL and a too small one HHFM_EWORKSPACE (also at B = 0), before
+ * anything is launched: a refusal leaves every parameter, slot and the
+ * workspace untouched. */
+int hhfm_afm_train_det_scratch(int64_t B, int32_t F, int32_t k, int32_t A, int64_t features_M,
+                               size_t* bytes);
+int hhfm_dfm_train_det_scratch(int64_t B, int32_t F, int32_t k, int64_t features_M,
+                               int32_t nlayers, const int32_t* layer_dims, size_t* bytes);
+int hhfm_afm_train_step_det(const int32_t* idx, const float* y, int64_t B, int32_t F, float* E,
+                            float* w, float* w0, int64_t features_M, int32_t k, int32_t A,
+                            float* W, float* b, float* pvec, float* P, float lr,
+                            float lambda_att, int32_t optimizer, float keep_att, float keep_afm,
+                            uint64_t seed, float* const* acc, void* workspace, size_t ws_bytes,
+                            void* scratch, size_t scratch_bytes, float* loss, void* stream);
+int hhfm_dfm_train_step_det(const int32_t* idx, const float* y, int64_t B, int32_t F, float* E,
+                            float* w, int64_t features_M, int32_t k, int32_t nlayers,
+                            const int32_t* layer_dims, float* const* W, float* const* bias,
+                            float* Wp, float* bp, float lr, float lambda_l2, int32_t optimizer,
+                            float* const* acc, void* workspace, size_t ws_bytes, void* scratch,
+                            size_t scratch_bytes, float* loss, void* stream);
 
 /* tf.nn.top_k(scores, K) over a materialised score matrix [B][ld] (first N
  * columns), K <= 64; ids reported as global_item_base + column. */

@@ -6,8 +6,10 @@ each.  Prints one JSON line: per case the sorted µs / step of 7 windows of 40
 steps; --drop adds FM at keep 0.5 and AFM at keep [0.8, 0.5]; --det adds an HHFM
 step (NG = 10) and the deterministic steps (FM at keep 1 and 0.5, HHFM) next
 to their default ones, and FM at B = 32,773 with one id in every row (the
-longest serial walk of the segment pass), default and deterministic.
-usage: python scripts/train_step_time.py LIBDIR TAG [--drop] [--det]"""
+longest serial walk of the segment pass), default and deterministic; --dfm adds
+the default DeepFM step (150/200/150), and --det, on a build that has them,
+also the deterministic AFM (keep 1 and [0.8, 0.5]) and DeepFM steps.
+usage: python scripts/train_step_time.py LIBDIR TAG [--drop] [--det] [--dfm]"""
 import importlib.machinery
 import importlib.util
 import json
@@ -151,5 +153,50 @@ if det:
     Xh, yh = dev(Xh), dev(rng.choice([1.0, -1.0], Bh).astype(np.float32))
     res["fm_hot32773_us"] = timed(fm_step(Xh, yh, Bh, 1.0, None), reps=3, n=10)
     res["fm_det_hot32773_us"] = timed(fm_step(Xh, yh, Bh, 1.0, scratch(Bh, F)), reps=3, n=10)
+
+if det or "--dfm" in sys.argv:
+    # DeepFM 150/200/150 (DFM.py:256), default step; with --det, on a build that
+    # has them, the deterministic AFM (keep 1 and [0.8, 0.5]) and DeepFM steps
+    layers = [150, 200, 150]
+    dims = [F * k] + layers
+    D = F + k + layers[-1]
+    shapes = ([(M, k), (M,)] + [(i, o_) for i, o_ in zip(dims, dims[1:])] + [(o_,) for o_ in layers]
+              + [(D,), (1,)])
+    dpar, dacc = params(shapes, [0.01, 0.3] + [0.08] * 3 + [0.08] * 3 + [0.1, 0.01])
+    dp, da = [t.data_ptr() for t in dpar], [t.data_ptr() for t in dacc]
+    dws = torch.zeros(nat.dfm_train_workspace(B, F, k, M, layers), dtype=torch.uint8,
+                      device="cuda")
+
+    def dfm_step(sc):
+        def fn():
+            args = (X.data_ptr(), y.data_ptr(), B, F, dp[0], dp[1], M, k, layers, dp[2:5], dp[5:8],
+                    dp[8], dp[9], 0.01, 0.01, 0, da, dws.data_ptr(), dws.numel())
+            if sc is None:
+                nat.dfm_train_step(*args, loss.data_ptr(), st)
+            else:
+                nat.dfm_train_step_det(*args, sc.data_ptr(), sc.numel(), loss.data_ptr(), st)
+        return fn
+
+    def afm_step(keep, sc):
+        def fn():
+            step[0] += 1
+            args = (X.data_ptr(), y.data_ptr(), B, F, *ap[:3], M, k, A, *ap[3:], 0.1, 100.0, 0,
+                    keep[0], keep[1], 2016 | step[0] << 32, aa, aws.data_ptr(), aws.numel())
+            if sc is None:
+                nat.afm_train_step_ex(*args, loss.data_ptr(), st)
+            else:
+                nat.afm_train_step_det(*args, sc.data_ptr(), sc.numel(), loss.data_ptr(), st)
+        return fn
+
+    res["dfm_us"] = timed(dfm_step(None))
+    if det and hasattr(nat, "afm_train_step_det"):
+        asc = torch.empty(nat.afm_train_det_scratch(B, F, k, A, M), dtype=torch.uint8,
+                          device="cuda")
+        dsc = torch.empty(nat.dfm_train_det_scratch(B, F, k, M, layers), dtype=torch.uint8,
+                          device="cuda")
+        res["afm_det_keep1_us"] = timed(afm_step((1.0, 1.0), asc))
+        res["afm_keep0.8_0.5_us"] = timed(afm_step((0.8, 0.5), None))
+        res["afm_det_keep0.8_0.5_us"] = timed(afm_step((0.8, 0.5), asc))
+        res["dfm_det_us"] = timed(dfm_step(dsc))
 res = {k_: ([round(v, 2) for v in vs] if isinstance(vs, list) else vs) for k_, vs in res.items()}
 print(json.dumps(res))

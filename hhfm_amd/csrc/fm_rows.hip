@@ -203,7 +203,25 @@ __global__ __launch_bounds__(256) void fm_rows_fast(
 #ifndef HHFM_K1_HOT_AUTO
 #define HHFM_K1_HOT_AUTO 1   // 0: only HHFM_FLAG_HOT_TAIL selects the kernel
 #endif
+// Where the LDS-tail loop takes the user's and the item's `w` from:
+//   0  one vector load per slot (lanes sub = 0, 1 own fields 0, 1);
+//   1  fp32 tables, F <= 5, LPR >= 16: scalar loads.  A row's ids are the
+//      same in all LPR lanes of its group, so each (slot, field, group) is one wave-uniform address,
+//      fetched through the scalar data cache (counted on lgkmcnt, not on the
+//      in-order vmcnt of the row loads, and not a request to TA / vector L1)
+//      and put into lanes sub = 0, 1 by v_writelane.  3.483 -> 3.108 ms at
+//      configs[1] (profiles/k1_w_scalar_ab.txt).
+#ifndef HHFM_K1_W_SCALAR
+#define HHFM_K1_W_SCALAR 1
+#endif
 constexpr int kHotWindowBytes = 16384;
+// scalar `w` loads of a wave-iteration at most (more: the vector load), and
+// how many results are held in SGPRs at a time
+constexpr int kHotWScalarMax = 48;
+#ifndef HHFM_K1_W_SCALAR_BATCH
+#define HHFM_K1_W_SCALAR_BATCH 24
+#endif
+constexpr int kHotWScalarBatch = HHFM_K1_W_SCALAR_BATCH;
 
 // Row slots of the two loops, sized so that the kernel stays within the 168
 // VGPRs of 3 waves per SIMD (profiles/k1_hot_tail_resources.txt; the bf16
@@ -261,6 +279,12 @@ __global__ __launch_bounds__(256) void fm_rows_fast_hot(
   constexpr int NC = F - 2;                            // fields read from LDS
   constexpr int PKW = (NC + 3) / 4;                    // 4 local indices per register
   constexpr int WPL = (F + LPR - 1) / LPR;
+  // user / item `w` by scalar loads (HHFM_K1_W_SCALAR): fp32 tables, F <= 5,
+  // LPR >= 16 (2 * U * RPW <= 48).  F >= 6 spills more SGPRs inside the loop
+  // with them (F = 8 bf16 LPR 16: 1.21 -> 1.45 ms) and bf16 F = 5 LPR 16 ran
+  // 1.5 % slower (profiles/k1_w_scalar_ab.txt): those keep the vector load.
+  constexpr bool WS = HAS_W && HHFM_K1_W_SCALAR == 1 && !BF16 && F <= 5 &&
+                      2 * U * RPW <= kHotWScalarMax;
   static_assert(T <= 256, "local index is 8 bits");
   using C = Chunk<BF16>;
   const uint32_t M32 = id_limit32(M);
@@ -332,9 +356,40 @@ __global__ __launch_bounds__(256) void fm_rows_fast_hot(
         for (int f = 0; f < 2; ++f)
           c01[u][f].template load<NT01>(E + (int64_t)id01[u][f] * ROW_BYTES + sub * 16);
       }
-      // `w` of the user and item from global memory: lanes sub = 0, 1 own
-      // fields 0, 1 (the other lanes' load is dropped, as in fm_rows_fast)
-      if constexpr (HAS_W) {
+      // `w` of the user and item from global memory into lanes sub = 0, 1
+      // (fields 0, 1) of wg: by scalar loads (HHFM_K1_W_SCALAR), else by one
+      // vector load per slot (the other lanes' load is dropped, as in
+      // fm_rows_fast).  Rows >= B and clamped ids read w[0] either way.
+      if constexpr (WS) {
+        // The loop is wave-uniform (the __ballot above): EXEC is full, as
+        // v_readlane needs.  The row loads above are already in flight; a
+        // batch of scalar loads is issued, waited for on lgkmcnt and moved to
+        // lanes sub = 0 (user), 1 (item) of its slots' wg before the next,
+        // so no more than kHotWScalarBatch results are held in SGPRs at once
+        // and none across the consume phase (all 48 at once spill SGPRs in the
+        // loop).  The scheduling barriers keep one load's address arithmetic
+        // (64-bit: w + 4 * id for any features_M) from being hoisted over
+        // another's, which would hold an address pair per load.
+        constexpr int SB = kHotWScalarBatch / (2 * RPW);   // slots per batch
+#pragma unroll
+        for (int u0 = 0; u0 < U; u0 += SB) {
+          float wsc[SB][2][RPW];   // [slot][field][group], SGPRs
+#pragma unroll
+          for (int u = u0; u < u0 + SB && u < U; ++u)
+#pragma unroll
+            for (int gg = 0; gg < RPW; ++gg)
+#pragma unroll
+              for (int f = 0; f < 2; ++f) {
+                __builtin_amdgcn_sched_barrier(0);
+                wsc[u - u0][f][gg] = w[(int64_t)__builtin_amdgcn_readlane(id01[u][f], gg * LPR)];
+              }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int u = u0; u < u0 + SB && u < U; ++u)
+            wg[u] = __int_as_float(write_group_lanes01<LPR, RPW>(0, wsc[u - u0]));
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      } else if constexpr (HAS_W) {
 #pragma unroll
         for (int u = 0; u < U; ++u) wg[u] = w[sub == 1 ? id01[u][1] : id01[u][0]];
       }

@@ -148,6 +148,25 @@ HHFM_DEV float group_sum_dpp(float x) {
   return x;
 }
 
+// `v` with lane LANE replaced by the wave-uniform `s` (v_writelane_b32; this
+// compiler has the readlane builtin but none for writelane)
+template <int LANE>
+HHFM_DEV int write_lane(int v, int s) {
+  static_assert(LANE >= 0 && LANE < kWave, "lane of the wave");
+  asm("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(s), "n"(LANE));
+  return v;
+}
+// lanes 0, 1 of every group of LPR lanes: lane gg * LPR + f <- s[f][gg]
+template <int LPR, int RPW, int I = 0>
+HHFM_DEV int write_group_lanes01(int v, const float (&s)[2][RPW]) {
+  if constexpr (I < 2 * RPW) {
+    v = write_lane<(I >> 1) * LPR + (I & 1)>(v, __float_as_int(s[I & 1][I >> 1]));
+    return write_group_lanes01<LPR, RPW, I + 1>(v, s);
+  } else {
+    return v;
+  }
+}
+
 // 32-bit form of clamp_id for kernels that clamp many ids per iteration:
 // M32 = id_limit32(M) once per kernel; an int32 id is in [0, M) iff
 // (uint32_t)id < M32 (a negative id is >= 2^31 as unsigned).

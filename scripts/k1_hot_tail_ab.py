@@ -7,6 +7,8 @@ fm_rows_fast in one process, timed with HIP events after warm-up.
          default kernel) against flags 0 (the automatic rule)
   miss   the same table with all five columns uniform over [0, M): every
          wave leaves the LDS loop in its first iteration (the cliff guard)
+  wprice the hit leg's table and rows under the automatic rule (flags 0), with
+         `w` and with w=None: what the user / item `w` terms cost this kernel
   --shapes F:k:dtype,...  further Frappe-layout shapes (2^23 rows, 2 M users
          + 2 M items + 12 context ids), the same two flags
 
@@ -55,6 +57,15 @@ def ab(idx, E, w, reps):
     return out
 
 
+def w_price(idx, E, w, reps):
+    out = {}
+    o = torch.empty(idx.shape[0], dtype=torch.float32, device=idx.device)
+    for name, ww in (("with_w", w), ("without_w", None)):
+        out[name] = time_ms(lambda: ops.fm_score_rows(idx, E, ww, 0.0, out=o, flags=0), reps)
+    out["price_ms"] = out["with_w"]["median_ms"] - out["without_w"]["median_ms"]
+    return out
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--reps", type=int, default=20)
@@ -65,6 +76,7 @@ def main():
     res = {}
     idx, E, w, M = bench.make_batch(a.rows, 8 << 20, 8 << 20, 64, 1, dev)
     res["hit"] = ab(idx, E, w, a.reps)
+    res["wprice"] = w_price(idx, E, w, a.reps)
     g = torch.Generator(device=dev)
     g.manual_seed(7)
     idx = torch.randint(0, M, idx.shape, generator=g, device=dev, dtype=torch.int32)

@@ -6,8 +6,10 @@ assembly and, for every kernel whose demangled name contains --kernel, prints
 VGPRs, scratch and, for its largest loops (the blocks the compiler annotates
 with one loop header; in fm_rows_fast_hot the LDS-tail loop, then the general
 loop), the counts the consume phase is judged by: VALU, DPP-folded
-VALU, ds_bpermute_b32, other LDS, s_waitcnt, s_nop, global loads / stores and
-64-bit compares.
+VALU, ds_bpermute_b32, other LDS, s_waitcnt, s_nop, global loads / stores,
+64-bit compares, scalar dword loads (the user / item `w` of the LDS-tail loop),
+v_readlane / v_writelane (SGPR spill traffic shows up as more of these than the
+`w` path's own) and the s_waitcnt that drain lgkmcnt to 0.
 
   python scripts/k1_isa_mix.py --kernel "fm_rows_fast_hot<5, 16, false, true, true>"
 """
@@ -70,6 +72,11 @@ def mix(lines):
         "global_load_dwordx4": n(lambda i: i == "global_load_dwordx4"),
         "global_load_dword": n(lambda i: i == "global_load_dword"),
         "global_store": n(lambda i: i.startswith("global_store")),
+        "s_load_dword": n(lambda i: i == "s_load_dword"),
+        "s_load_wide": n(lambda i: i.startswith("s_load_dwordx")),
+        "v_readlane": n(lambda i: i.startswith("v_readlane")),
+        "v_writelane": n(lambda i: i.startswith("v_writelane")),
+        "lgkmcnt0": sum(1 for l in lines if re.match(r"^\s+s_waitcnt\b.*lgkmcnt\(0\)", l)),
         "v_cmp_u64": n(lambda i: re.match(r"v_cmp\w*_u64", i) is not None),
         "v_cmp_i64": n(lambda i: re.match(r"v_cmp\w*_i64", i) is not None),
     }

@@ -1,8 +1,15 @@
 """HHFM (OurModel7) — drop-in for Newcode/OurModel7.py (OUR, Train, M7_main).
 
-Sum pooling everywhere (the committed setting, OurModel7.py:14-19), so the
-pairwise-product branches of the reference graph are dead code and
+The pairwise-product branches of the reference graph are dead code (their
+Pooling2* results are never used), so with the committed sum pooling
+(OurModel7.py:14-19)
   h = E[user] + Σ E[ctx] (+ Σ E[time]),   score = h · E[item]   (no bias).
+The three live pools follow the module attributes ``Pooling1C`` (context rows),
+``Pooling1T`` (time rows) and ``Pooling1F`` (the stack {user, context pool,
+time pool}), read when an ``OUR`` is constructed: "sum", "max" or "mean" (or
+``ops.POOL_*``), as the reference sets tf.reduce_sum / reduce_max /
+reduce_mean there; ``OUR(..., pooling=(ctx, time, final))`` and ``--pooling``
+override them.  ``Pooling2C`` / ``2T`` / ``2F`` are accepted and ignored.
 Scoring runs on the gfx950 kernels:
   * ``score_rows`` / ``sess.run(model.PositiveFeadback)`` -> hhfm_hybrid_score_rows
     (OurModel7.py:105-171)
@@ -20,6 +27,27 @@ from . import harness, ops
 from ._model import Fetch, Placeholder, ScoringModel, rows_from
 
 method = "M7"
+
+# OurModel7.py:14-19.  Pooling2* feed results the reference's graph never uses.
+Pooling1C = "sum"
+Pooling2C = "sum"
+Pooling1T = "sum"
+Pooling2T = "sum"
+Pooling1F = "sum"
+Pooling2F = "sum"
+
+
+def parse_pooling(text):
+    """``--pooling``: "max" / "mean" / "sum" (all three pools) or
+    "ctx,time,final" -> a (ctx, time, final) triple of mode names."""
+    parts = [t.strip() for t in str(text).split(",")]
+    if len(parts) == 1:
+        parts = parts * 3
+    if len(parts) != 3:
+        raise ValueError(f"--pooling takes one mode or ctx,time,final, got {text!r}")
+    for t in parts:
+        ops.pool_mode(t)
+    return tuple(parts)
 
 
 def parse_args(dataname, factor, Topk, argv=None):
@@ -40,6 +68,9 @@ def parse_args(dataname, factor, Topk, argv=None):
     p.add_argument("--result_file", default="../result.txt")
     p.add_argument("--deterministic", type=int, default=0,
                    help="1: bit-reproducible training steps (row-ordered sums)")
+    p.add_argument("--pooling", default=None,
+                   help="max | mean | sum, or ctx,time,final (default: the module's "
+                        "Pooling1C / Pooling1T / Pooling1F)")
     return p.parse_args(argv)
 
 
@@ -47,8 +78,14 @@ class OUR(ScoringModel):
     def __init__(self, feature_dimension, time_dimension, features_M, n_user, n_item,
                  hidden_factor, learning_rate, lamda_bilinear, optimizer_type, context, time,
                  random_seed=2016, device=None, table_dtype=torch.float32,
-                 deterministic=False):
+                 deterministic=False, pooling=None):
         self.deterministic = bool(deterministic)
+        if pooling is None:
+            pooling = (Pooling1C, Pooling1T, Pooling1F)
+        elif isinstance(pooling, str):
+            pooling = parse_pooling(pooling)
+        # None: the sum-pooling entry points, exactly as before
+        self.pooling = tuple(pooling) if ops.pooling_word(pooling) != 0 else None
         self.feature_dimension = feature_dimension
         self.time_dimension = time_dimension
         self.n_user = n_user
@@ -100,7 +137,7 @@ class OUR(ScoringModel):
         """PositiveFeadback for full rows [user, item, ctx..., time...] -> [B,1]."""
         idx = self._idx(X)
         ctx, tim = self._ranges(idx.shape[1])
-        out = ops.hybrid_score_rows(idx, self.table, 0, 1, ctx, tim)
+        out = ops.hybrid_score_rows(idx, self.table, 0, 1, ctx, tim, pooling=self.pooling)
         return self._np_out(out)
 
     def catalog_topk(self, q, begin, count, K):
@@ -108,7 +145,7 @@ class OUR(ScoringModel):
         -> (scores, global item offsets) device tensors [B, K]."""
         ctx, tim = self._ranges(q.shape[1])
         return ops.catalog_topk(q, self.table, ops.MODE_HHFM, int(K), self.n_user + begin,
-                                count, begin, None, 0, ctx, tim)
+                                count, begin, None, 0, ctx, tim, pooling=self.pooling)
 
     def topk(self, A, tp):
         _, ids = self.catalog_topk(self._idx(A), 0, self.n_item, tp)
@@ -148,7 +185,8 @@ class Train(harness.Train):
         self.model = model if model is not None else OUR(
             self.feature_dimension, self.time_dimension, self.features_M, self.n_user,
             self.n_item, args.hidden_factor, args.lr, args.lamda, args.optimizer,
-            self.context, self.time, deterministic=bool(getattr(args, "deterministic", 0)))
+            self.context, self.time, deterministic=bool(getattr(args, "deterministic", 0)),
+            pooling=getattr(args, "pooling", None))
 
     def train(self):
         from .training import run_training_hhfm

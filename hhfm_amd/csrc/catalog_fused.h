@@ -276,7 +276,10 @@ HHFM_DEV void sort_scores2(float& s0, float& s1) {
 // workgroups per CU, for grids past one workgroup per CU: 3,000 queries 33.0
 // -> 28.2 us) or in registers (one workgroup per CU: 300 queries 17.3 us
 // against 19.5 with QL)
-template <bool BF16, int KT, bool FM, bool SPLIT, int T, bool QL>
+// POOL (HHFM only): step 0 forms the MAX / MEAN pooled h of hhfm_pool.h
+// (include/hhfm.h "Pooling"); the modes travel in the otherwise unused `mode`
+// argument, HHFM_MODE_HHFM | pooling << 8.  Everything after step 0 is the same.
+template <bool BF16, int KT, bool FM, bool SPLIT, int T, bool QL, bool POOL = false>
 __global__ __launch_bounds__(kFusedWaves * 64) void catalog_fused(
     const int32_t* __restrict__ qidx, int64_t B, int ncols, int mode, int ucol, int c0, int c1,
     int t0, int t1, const char* __restrict__ E, int64_t M, int64_t item_row_begin, int32_t N,
@@ -420,8 +423,13 @@ __global__ __launch_bounds__(kFusedWaves * 64) void catalog_fused(
           // four rows in flight per step (rolled: one body fetched)
           float uu[EPC], cx[EPC], tm[EPC], r[EPC];
           const uint4 ru = ld(0);
+          [[maybe_unused]] const PoolModes pm{(mode >> 8) & 15, (mode >> 12) & 15,
+                                              (mode >> 16) & 15};
 #pragma unroll
-          for (int v = 0; v < EPC; ++v) cx[v] = tm[v] = 0.f;
+          for (int v = 0; v < EPC; ++v) {
+            cx[v] = POOL ? pool_identity(pm.ctx) : 0.f;
+            tm[v] = POOL ? pool_identity(pm.tim) : 0.f;
+          }
 #pragma unroll 1
           for (int f0 = 1; f0 < nf; f0 += 4) {
             uint4 rr[4];
@@ -432,7 +440,15 @@ __global__ __launch_bounds__(kFusedWaves * 64) void catalog_fused(
               const int f = f0 + x;   // wave-uniform
               if (f >= nf) break;
               cvt(rr[x], r);
-              if (f <= nc) {
+              if constexpr (POOL) {
+                if (f <= nc) {
+#pragma unroll
+                  for (int v = 0; v < EPC; ++v) cx[v] = pool_step(pm.ctx, cx[v], r[v]);
+                } else {
+#pragma unroll
+                  for (int v = 0; v < EPC; ++v) tm[v] = pool_step(pm.tim, tm[v], r[v]);
+                }
+              } else if (f <= nc) {
 #pragma unroll
                 for (int v = 0; v < EPC; ++v) cx[v] += r[v];
               } else {
@@ -449,6 +465,9 @@ __global__ __launch_bounds__(kFusedWaves * 64) void catalog_fused(
               if constexpr (FM) {
                 hv = uu[v] + cx[v];                     // FM.py:177
                 part[cc % LPT][v] += hv * cx[v];        // FM.py:178-183
+              } else if constexpr (POOL) {
+                hv = pool_h(uu[v], pool_finish(pm.ctx, cx[v], nc), nc,
+                            pool_finish(pm.tim, tm[v], nt), nt, pm.fin);
               } else {
                 hv = uu[v];                             // OurModel7.py:270-292
                 if (c1 > c0) hv = hv + cx[v];

@@ -22,6 +22,7 @@
 //     rank lists gathered over RCCL) into the final top-K.
 // Order everywhere: score descending, item index ascending (tf.nn.top_k).
 #include "gemm_mfma.h"
+#include "hhfm_pool.h"
 
 #include <algorithm>
 
@@ -116,6 +117,41 @@ __global__ __launch_bounds__(256) void catalog_queries(
     }
     part = group_sum<kWave>(part);
     if (lane == 0) cst[b] = part;
+  }
+}
+
+// HHFM_MODE_HHFM with MAX / MEAN pooling (include/hhfm.h "Pooling"): the same
+// walk with h from hhfm_pool.h — the row kernels' h bit for bit; cst stays 0.
+// A kernel of its own, so that catalog_queries keeps its code and registers.
+template <bool BF16>
+__global__ __launch_bounds__(256) void catalog_queries_pool(
+    const int32_t* __restrict__ qidx, int64_t B, int64_t Bpad, int ncols,
+    int ucol, int c0, int c1, int t0, int t1, const char* __restrict__ E, int64_t M,
+    int k, PoolModes pm, float* __restrict__ H, float* __restrict__ cst) {
+  const int lane = lane_id();
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const int esz = BF16 ? 2 : 4;
+  auto val = [&](int32_t id, int e) -> float {
+    const char* r = E + (int64_t)clamp_id(id, M) * k * esz;
+    return BF16 ? bf16_to_f32(reinterpret_cast<const uint16_t*>(r)[e])
+                : reinterpret_cast<const float*>(r)[e];
+  };
+  for (int64_t b = wave; b < Bpad; b += nwave) {
+    if (b < B) {
+      const int32_t* p = qidx + b * (int64_t)ncols;
+      for (int e = lane; e < k; e += kWave) {
+        float cv = pool_identity(pm.ctx), tv = pool_identity(pm.tim);
+        for (int c = c0; c < c1; ++c) cv = pool_step(pm.ctx, cv, val(p[c], e));
+        for (int c = t0; c < t1; ++c) tv = pool_step(pm.tim, tv, val(p[c], e));
+        cv = pool_finish(pm.ctx, cv, c1 - c0);
+        tv = pool_finish(pm.tim, tv, t1 - t0);
+        H[b * k + e] = pool_h(val(p[ucol], e), cv, c1 - c0, tv, t1 - t0, pm.fin);
+      }
+    } else {
+      for (int e = lane; e < k; e += kWave) H[b * k + e] = 0.f;
+    }
+    if (lane == 0) cst[b] = 0.f;
   }
 }
 
@@ -1246,7 +1282,7 @@ static void launch_store(int64_t B, int nqb, int32_t N, const float* H, const fl
 // the fused small-catalog kernel (catalog_fused.h): S 8-wave workgroups per
 // 32 queries, each over one range of 8 x kFusedTiles item tiles; the last to
 // finish merges the S range lists
-template <bool BF16, int KT, bool FM, int T>
+template <bool BF16, int KT, bool FM, int T, bool POOL>
 static void launch_fused_t(int64_t B, int S, const int32_t* qidx, int ncols, int mode, int ucol,
                          int c0, int c1, int t0, int t1, const char* E, int64_t M, int64_t irb,
                          int32_t N, const float* w, int K, float* os, int32_t* oi, int32_t gbase,
@@ -1257,7 +1293,7 @@ static void launch_fused_t(int64_t B, int S, const int32_t* qidx, int ncols, int
   // workgroups per CU); below it they stay in registers
   const bool ql = (int64_t)nqb * S > 256;
 #define HHFM_FL(SP, QL_)                                                                       \
-  hipLaunchKernelGGL((catalog_fused<BF16, KT, FM, SP, T, QL_>), dim3(nqb * S),                 \
+  hipLaunchKernelGGL((catalog_fused<BF16, KT, FM, SP, T, QL_, POOL>), dim3(nqb * S),                \
                      dim3(kFusedWaves * 64), 0, st, qidx, B, ncols, mode, ucol, c0, c1, t0, t1, \
                      E, M, irb, N, w, K, os, oi, gbase, S, arrive, part)
   if (kCanSplit && !(plan & HHFM_PLAN_EXACT_FP32)) {
@@ -1269,29 +1305,30 @@ static void launch_fused_t(int64_t B, int S, const int32_t* qidx, int ncols, int
 #undef HHFM_FL
 }
 
-template <bool BF16, int KT, bool FM>
+template <bool BF16, int KT, bool FM, bool POOL>
 static void launch_fused(int64_t B, int S, int T, const int32_t* qidx, int ncols, int mode,
                          int ucol, int c0, int c1, int t0, int t1, const char* E, int64_t M,
                          int64_t irb, int32_t N, const float* w, int K, float* os, int32_t* oi,
                          int32_t gbase, uint32_t* arrive, uint64_t* part, int32_t plan,
                          hipStream_t st) {
   if (T == 2)
-    launch_fused_t<BF16, KT, FM, 2>(B, S, qidx, ncols, mode, ucol, c0, c1, t0, t1, E, M, irb, N,
+    launch_fused_t<BF16, KT, FM, 2, POOL>(B, S, qidx, ncols, mode, ucol, c0, c1, t0, t1, E, M, irb, N,
                                     w, K, os, oi, gbase, arrive, part, plan, st);
   else
-    launch_fused_t<BF16, KT, FM, kFusedTiles>(B, S, qidx, ncols, mode, ucol, c0, c1, t0, t1, E,
-                                              M, irb, N, w, K, os, oi, gbase, arrive, part, plan,
-                                              st);
+    launch_fused_t<BF16, KT, FM, kFusedTiles, POOL>(B, S, qidx, ncols, mode, ucol, c0, c1, t0, t1,
+                                                    E, M, irb, N, w, K, os, oi, gbase, arrive, part,
+                                                    plan, st);
 }
 
-template <bool BF16, bool FM>
+// POOL: `mode` carries HHFM_MODE_HHFM | pooling << 8 (catalog_fused.h)
+template <bool BF16, bool FM, bool POOL = false>
 static bool dispatch_fused(int KT, int64_t B, int S, int T, const int32_t* qidx, int ncols, int mode,
                            int ucol, int c0, int c1, int t0, int t1, const char* E, int64_t M,
                            int64_t irb, int32_t N, const float* w, int K, float* os, int32_t* oi,
                            int32_t gbase, uint32_t* arrive, uint64_t* part, int32_t plan,
                            hipStream_t st) {
 #define HHFM_FUSED(KT_) \
-  launch_fused<BF16, KT_, FM>(B, S, T, qidx, ncols, mode, ucol, c0, c1, t0, t1, E, M, irb, N, w, K, \
+  launch_fused<BF16, KT_, FM, POOL>(B, S, T, qidx, ncols, mode, ucol, c0, c1, t0, t1, E, M, irb, N, w, K, \
                               os, oi, gbase, arrive, part, plan, st)
   switch (KT) {
     case 1: HHFM_FUSED(1); break;
@@ -1399,13 +1436,20 @@ extern "C" int hhfm_catalog_topk(
                               HHFM_PLAN_DEFAULT, nullptr, stream);
 }
 
-extern "C" int hhfm_catalog_topk_ex(
+// hhfm_catalog_topk_ex (pooling 0) and hhfm_catalog_topk_pool: a pooled call
+// differs in how h is formed alone — catalog_queries_pool, or the POOL form of
+// the fused small-catalog kernel's step 0.
+static int catalog_topk_impl(
     const int32_t* qidx, int64_t B, int32_t ncols, int32_t mode,
     int32_t user_col, int32_t ctx_begin, int32_t ctx_end, int32_t time_begin,
     int32_t time_end, const void* E, int64_t features_M, int32_t k,
     int32_t dtype, const float* w, int32_t item_row_begin, int32_t item_count,
     int32_t global_item_base, int32_t K, float* top_score, int32_t* top_idx,
-    void* workspace, size_t ws_bytes, int32_t plan, int32_t* status, void* stream) {
+    void* workspace, size_t ws_bytes, int32_t plan, int32_t pooling, int32_t* status,
+    void* stream) {
+  PoolModes pm;
+  if (!pooling_unpack(pooling, pm)) return HHFM_EINVAL;
+  if (pooling != 0 && mode == HHFM_MODE_FM) return HHFM_EINVAL;
   if (B < 0 || ncols < 1 || ncols > 64 || k < 1 || features_M < 1) return HHFM_EINVAL;
   if (plan & ~HHFM_PLAN_ALL) return HHFM_EINVAL;
   if (dtype != HHFM_F32 && dtype != HHFM_BF16) return HHFM_EINVAL;
@@ -1455,13 +1499,17 @@ extern "C" int hhfm_catalog_topk_ex(
     const float* wv = (fmm && w) ? w : nullptr;
     uint32_t* arrive = reinterpret_cast<uint32_t*>(ws);
     uint64_t* part = reinterpret_cast<uint64_t*>(ws + p.off_sc);
-#define HHFM_FARGS KT, B, p.fS, p.fT, qidx, ncols, mode, user_col, ctx_begin, ctx_end, time_begin, \
+    const int kmode = mode | pooling << 8;   // the fused kernel's POOL form reads the modes here
+#define HHFM_FARGS KT, B, p.fS, p.fT, qidx, ncols, kmode, user_col, ctx_begin, ctx_end, time_begin, \
     time_end, Eb, features_M, (int64_t)item_row_begin, item_count, wv, K, top_score, top_idx, \
     global_item_base, arrive, part, plan, st
-    const bool ok = bf16 ? (fmm ? dispatch_fused<true, true>(HHFM_FARGS)
-                                : dispatch_fused<true, false>(HHFM_FARGS))
-                         : (fmm ? dispatch_fused<false, true>(HHFM_FARGS)
-                                : dispatch_fused<false, false>(HHFM_FARGS));
+    const bool ok = pooling != 0
+                        ? (bf16 ? dispatch_fused<true, false, true>(HHFM_FARGS)
+                                : dispatch_fused<false, false, true>(HHFM_FARGS))
+                        : bf16 ? (fmm ? dispatch_fused<true, true>(HHFM_FARGS)
+                                      : dispatch_fused<true, false>(HHFM_FARGS))
+                               : (fmm ? dispatch_fused<false, true>(HHFM_FARGS)
+                                      : dispatch_fused<false, false>(HHFM_FARGS));
 #undef HHFM_FARGS
     if (ok) return (int)hipGetLastError();
   }
@@ -1469,7 +1517,15 @@ extern "C" int hhfm_catalog_topk_ex(
   {
     int64_t blocks = (p.Bpad + 3) / 4;
     if (blocks > 4096) blocks = 4096;
-    if (bf16)
+    if (pooling != 0 && bf16)
+      hipLaunchKernelGGL(catalog_queries_pool<true>, dim3((int)blocks), dim3(256), 0, st,
+                         qidx, B, p.Bpad, ncols, user_col, ctx_begin, ctx_end, time_begin,
+                         time_end, Eb, features_M, k, pm, H, cst);
+    else if (pooling != 0)
+      hipLaunchKernelGGL(catalog_queries_pool<false>, dim3((int)blocks), dim3(256), 0, st,
+                         qidx, B, p.Bpad, ncols, user_col, ctx_begin, ctx_end, time_begin,
+                         time_end, Eb, features_M, k, pm, H, cst);
+    else if (bf16)
       hipLaunchKernelGGL(catalog_queries<true>, dim3((int)blocks), dim3(256), 0, st,
                          qidx, B, p.Bpad, ncols, mode, user_col, ctx_begin,
                          ctx_end, time_begin, time_end, Eb, features_M, k, H, cst);
@@ -1584,6 +1640,33 @@ extern "C" int hhfm_catalog_topk_ex(
                  top_score, top_idx, st);
   }
   return (int)hipGetLastError();
+}
+
+extern "C" int hhfm_catalog_topk_ex(
+    const int32_t* qidx, int64_t B, int32_t ncols, int32_t mode,
+    int32_t user_col, int32_t ctx_begin, int32_t ctx_end, int32_t time_begin,
+    int32_t time_end, const void* E, int64_t features_M, int32_t k,
+    int32_t dtype, const float* w, int32_t item_row_begin, int32_t item_count,
+    int32_t global_item_base, int32_t K, float* top_score, int32_t* top_idx,
+    void* workspace, size_t ws_bytes, int32_t plan, int32_t* status, void* stream) {
+  return catalog_topk_impl(qidx, B, ncols, mode, user_col, ctx_begin, ctx_end, time_begin,
+                           time_end, E, features_M, k, dtype, w, item_row_begin, item_count,
+                           global_item_base, K, top_score, top_idx, workspace, ws_bytes, plan,
+                           0, status, stream);
+}
+
+extern "C" int hhfm_catalog_topk_pool(
+    const int32_t* qidx, int64_t B, int32_t ncols, int32_t mode,
+    int32_t user_col, int32_t ctx_begin, int32_t ctx_end, int32_t time_begin,
+    int32_t time_end, const void* E, int64_t features_M, int32_t k,
+    int32_t dtype, const float* w, int32_t item_row_begin, int32_t item_count,
+    int32_t global_item_base, int32_t K, float* top_score, int32_t* top_idx,
+    void* workspace, size_t ws_bytes, int32_t plan, int32_t pooling, int32_t* status,
+    void* stream) {
+  return catalog_topk_impl(qidx, B, ncols, mode, user_col, ctx_begin, ctx_end, time_begin,
+                           time_end, E, features_M, k, dtype, w, item_row_begin, item_count,
+                           global_item_base, K, top_score, top_idx, workspace, ws_bytes, plan,
+                           pooling, status, stream);
 }
 
 #if HHFM_FUSED_TIMING

@@ -17,6 +17,7 @@
 //     the xor-32/16 steps of LPR 64 / 32 go through ds_bpermute_b32 (LDS
 //     hardware, no LDS allocation).  No atomics, one fp32 store per row.
 #include "hhfm_common.h"
+#include "hhfm_pool.h"
 
 namespace hhfm {
 
@@ -637,6 +638,163 @@ __global__ __launch_bounds__(256) void hybrid_rows_generic(
 }
 
 // ---------------------------------------------------------------------------
+// HHFM row kernels with MAX / MEAN pooling (include/hhfm.h "Pooling";
+// hhfm_pool.h).  hybrid_rows_pool is hybrid_rows_fast's load phase unchanged —
+// the same F x LPR switch, load_ids, unconditional clamped loads, U rows in
+// flight, group_sum_dpp — and a consume phase that steps one accumulator per
+// pool and element by the modes, which are wave-uniform kernel arguments
+// (SGPRs), not template parameters.
+// ---------------------------------------------------------------------------
+template <int F, int LPR, bool BF16>
+__global__ __launch_bounds__(256) void hybrid_rows_pool(
+    const int32_t* __restrict__ idx, int64_t B, int nctx,
+    const char* __restrict__ E, int64_t M, float* __restrict__ out,
+    PoolModes pm, int32_t* __restrict__ status) {
+  constexpr int U = RowsPerLane<F>::value;
+  constexpr int RPW = kWave / LPR;
+  constexpr int RPI = RPW * U;
+  constexpr int64_t ROW_BYTES = (int64_t)LPR * 16;
+  using C = Chunk<BF16>;
+  const uint32_t M32 = id_limit32(M);
+
+  const int lane = threadIdx.x & (kWave - 1);
+  const int sub = lane & (LPR - 1);
+  const int g = lane / LPR;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const int64_t stride = nwave * RPI;
+  const int ctx_end = 2 + nctx;
+  const int ntime = F - ctx_end;
+  const bool cmax = pm.ctx == HHFM_POOL_MAX, tmax = pm.tim == HHFM_POOL_MAX;
+  const float cid = pool_identity(pm.ctx), tid = pool_identity(pm.tim);
+
+  int64_t base = wave * RPI;
+  int32_t raw[U][F];
+  bool bad = false;
+  if (base < B) load_ids<F, U>(raw, idx, base, B, g, RPW, F);
+
+  for (; base < B; base += stride) {
+    C c[U][F];
+    int32_t id[U][F];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int f = 0; f < F; ++f) {
+        id[u][f] = clamp_id32(raw[u][f], M32);
+        bad |= id[u][f] != raw[u][f];
+        c[u][f].load(E + (int64_t)id[u][f] * ROW_BYTES + sub * 16);
+      }
+
+    // (unconditional: rows past B read row 0, which keeps vmcnt counting exact)
+    load_ids<F, U>(raw, idx, base + stride, B, g, RPW, F);
+
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      float t = 0.f;
+      // one accumulator per pool and element; a field outside the pool steps
+      // in the identity (wave-uniform select), and the mode is branched on
+      // around the whole field x element block, so every block is straight-line
+      float cv[C::kElems], tv[C::kElems];
+      if (cmax) {
+#pragma unroll
+        for (int e = 0; e < C::kElems; ++e) cv[e] = cid;
+#pragma unroll
+        for (int f = 2; f < F; ++f)
+#pragma unroll
+          for (int e = 0; e < C::kElems; ++e)
+            cv[e] = pool_step(HHFM_POOL_MAX, cv[e], f < ctx_end ? c[u][f].v[e] : cid);
+      } else {
+#pragma unroll
+        for (int e = 0; e < C::kElems; ++e) cv[e] = cid;
+#pragma unroll
+        for (int f = 2; f < F; ++f)
+#pragma unroll
+          for (int e = 0; e < C::kElems; ++e)
+            cv[e] = pool_step(HHFM_POOL_SUM, cv[e], f < ctx_end ? c[u][f].v[e] : cid);
+        if (pm.ctx == HHFM_POOL_MEAN) {
+#pragma unroll
+          for (int e = 0; e < C::kElems; ++e) cv[e] = pool_finish(HHFM_POOL_MEAN, cv[e], nctx);
+        }
+      }
+      if (tmax) {
+#pragma unroll
+        for (int e = 0; e < C::kElems; ++e) tv[e] = tid;
+#pragma unroll
+        for (int f = 2; f < F; ++f)
+#pragma unroll
+          for (int e = 0; e < C::kElems; ++e)
+            tv[e] = pool_step(HHFM_POOL_MAX, tv[e], f < ctx_end ? tid : c[u][f].v[e]);
+      } else {
+#pragma unroll
+        for (int e = 0; e < C::kElems; ++e) tv[e] = tid;
+#pragma unroll
+        for (int f = 2; f < F; ++f)
+#pragma unroll
+          for (int e = 0; e < C::kElems; ++e)
+            tv[e] = pool_step(HHFM_POOL_SUM, tv[e], f < ctx_end ? tid : c[u][f].v[e]);
+        if (pm.tim == HHFM_POOL_MEAN) {
+#pragma unroll
+          for (int e = 0; e < C::kElems; ++e) tv[e] = pool_finish(HHFM_POOL_MEAN, tv[e], ntime);
+        }
+      }
+      if (pm.fin == HHFM_POOL_MAX) {
+#pragma unroll
+        for (int e = 0; e < C::kElems; ++e)
+          t += pool_h(c[u][0].v[e], cv[e], nctx, tv[e], ntime, HHFM_POOL_MAX) * c[u][1].v[e];
+      } else if (pm.fin == HHFM_POOL_MEAN) {
+#pragma unroll
+        for (int e = 0; e < C::kElems; ++e)
+          t += pool_h(c[u][0].v[e], cv[e], nctx, tv[e], ntime, HHFM_POOL_MEAN) * c[u][1].v[e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < C::kElems; ++e)
+          t += pool_h(c[u][0].v[e], cv[e], nctx, tv[e], ntime, HHFM_POOL_SUM) * c[u][1].v[e];
+      }
+      t = group_sum_dpp<LPR>(t);
+      const int64_t row = base + (int64_t)u * RPW + g;
+      if (sub == 0 && row < B) out[row] = t;
+    }
+  }
+  report_bad_id(status, bad);
+}
+
+// any layout, any k: hybrid_rows_generic with the pooled h
+template <bool BF16>
+__global__ __launch_bounds__(256) void hybrid_rows_generic_pool(
+    const int32_t* __restrict__ idx, int64_t B, int ncols, int ucol, int icol,
+    int c0, int c1, int t0, int t1, const char* __restrict__ E, int64_t M,
+    int k, float* __restrict__ out, PoolModes pm, int32_t* __restrict__ status) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const int esz = BF16 ? 2 : 4;
+  auto val = [&](int32_t id, int e) -> float {
+    const char* r = E + (int64_t)clamp_id(id, M) * k * esz;
+    return BF16 ? bf16_to_f32(reinterpret_cast<const uint16_t*>(r)[e])
+                : reinterpret_cast<const float*>(r)[e];
+  };
+  bool bad = false;
+  for (int64_t row = wave; row < B; row += nwave) {
+    const int32_t* p = idx + row * (int64_t)ncols;
+    for (int c = lane; c < ncols; c += kWave)
+      if (c == ucol || c == icol || (c >= c0 && c < c1) || (c >= t0 && c < t1))
+        bad |= clamp_id(p[c], M) != p[c];
+    float t = 0.f;
+    for (int e = lane; e < k; e += kWave) {
+      float cv = pool_identity(pm.ctx), tv = pool_identity(pm.tim);
+      for (int c = c0; c < c1; ++c) cv = pool_step(pm.ctx, cv, val(p[c], e));
+      for (int c = t0; c < t1; ++c) tv = pool_step(pm.tim, tv, val(p[c], e));
+      cv = pool_finish(pm.ctx, cv, c1 - c0);
+      tv = pool_finish(pm.tim, tv, t1 - t0);
+      t += pool_h(val(p[ucol], e), cv, c1 - c0, tv, t1 - t0, pm.fin) * val(p[icol], e);
+    }
+    t = group_sum<kWave>(t);
+    if (lane == 0) out[row] = t;
+  }
+  report_bad_id(status, bad);
+}
+
+// ---------------------------------------------------------------------------
 // dispatch
 // ---------------------------------------------------------------------------
 static int grid_for(int64_t rows, int64_t rows_per_block, hipStream_t s) {
@@ -709,6 +867,16 @@ static void launch_hybrid_fast(const int32_t* idx, int64_t B, int nctx,
                      s, idx, B, nctx, E, M, out, status);
 }
 
+template <int F, int LPR, bool BF16>
+static void launch_hybrid_pool(const int32_t* idx, int64_t B, int nctx,
+                               const char* E, int64_t M, float* out, PoolModes pm,
+                               int32_t* status, hipStream_t s) {
+  constexpr int RPB = 4 * (kWave / LPR) * RowsPerLane<F>::value;
+  const int grid = grid_for(B, RPB, s);
+  hipLaunchKernelGGL((hybrid_rows_pool<F, LPR, BF16>), dim3(grid), dim3(256), 0,
+                     s, idx, B, nctx, E, M, out, pm, status);
+}
+
 // dispatch on LPR (16-byte chunks per row) for a fixed F and dtype
 #define HHFM_LPR_SWITCH(LAUNCH, F, BF16, ...)            \
   switch (lpr) {                                         \
@@ -776,6 +944,17 @@ static bool try_hybrid_fast(const int32_t* idx, int64_t B, int F, int nctx,
     HHFM_F_SWITCH(launch_hybrid_fast, true, idx, B, nctx, E, M, out, status, s)
   } else {
     HHFM_F_SWITCH(launch_hybrid_fast, false, idx, B, nctx, E, M, out, status, s)
+  }
+  return true;
+}
+
+static bool try_hybrid_pool(const int32_t* idx, int64_t B, int F, int nctx,
+                            const char* E, int64_t M, int lpr, bool bf16,
+                            float* out, PoolModes pm, int32_t* status, hipStream_t s) {
+  if (bf16) {
+    HHFM_F_SWITCH(launch_hybrid_pool, true, idx, B, nctx, E, M, out, pm, status, s)
+  } else {
+    HHFM_F_SWITCH(launch_hybrid_pool, false, idx, B, nctx, E, M, out, pm, status, s)
   }
   return true;
 }
@@ -901,6 +1080,63 @@ extern "C" int hhfm_hybrid_score_rows(const int32_t* idx, int64_t B,
   return hhfm_hybrid_score_rows_ex(idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
                                    time_begin, time_end, E, features_M, k, dtype, out,
                                    nullptr, stream);
+}
+
+// H1 with pooling: pooling == 0 is hhfm_hybrid_score_rows_ex itself; any other
+// legal word runs hybrid_rows_pool (same shapes as hybrid_rows_fast) or
+// hybrid_rows_generic_pool.  Argument checks as in hhfm_hybrid_score_rows_ex.
+extern "C" int hhfm_hybrid_score_rows_pool(const int32_t* idx, int64_t B,
+                                           int32_t ncols, int32_t user_col,
+                                           int32_t item_col, int32_t ctx_begin,
+                                           int32_t ctx_end, int32_t time_begin,
+                                           int32_t time_end, const void* E,
+                                           int64_t features_M, int32_t k,
+                                           int32_t dtype, float* out, int32_t pooling,
+                                           int32_t* status, void* stream) {
+  PoolModes pm;
+  if (!pooling_unpack(pooling, pm)) return HHFM_EINVAL;
+  if (pooling == 0)
+    return hhfm_hybrid_score_rows_ex(idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
+                                     time_begin, time_end, E, features_M, k, dtype, out,
+                                     status, stream);
+  if (B < 0 || ncols < 2 || ncols > 64 || k < 1 || features_M < 1)
+    return HHFM_EINVAL;
+  if (dtype != HHFM_F32 && dtype != HHFM_BF16) return HHFM_EINVAL;
+  auto in_range = [&](int c) { return c >= 0 && c < ncols; };
+  if (!in_range(user_col) || !in_range(item_col)) return HHFM_EINVAL;
+  if (ctx_begin > ctx_end || time_begin > time_end) return HHFM_EINVAL;
+  if (ctx_end > ctx_begin && (!in_range(ctx_begin) || ctx_end > ncols))
+    return HHFM_EINVAL;
+  if (time_end > time_begin && (!in_range(time_begin) || time_end > ncols))
+    return HHFM_EINVAL;
+  if (B == 0) return HHFM_OK;
+  if (!idx || !E || !out) return HHFM_EINVAL;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool bf16 = dtype == HHFM_BF16;
+  const int lpr = lpr_for(k, dtype);
+  const bool aligned = (reinterpret_cast<uintptr_t>(E) & 15) == 0;
+  const int nctx = ctx_end - ctx_begin;
+  const int ntime = time_end - time_begin;
+  const bool canonical = user_col == 0 && item_col == 1 &&
+                         (nctx == 0 || ctx_begin == 2) &&
+                         (ntime == 0 || time_begin == 2 + nctx) &&
+                         2 + nctx + ntime == ncols;
+  if (!(canonical && lpr && aligned &&
+        try_hybrid_pool(idx, B, ncols, nctx, reinterpret_cast<const char*>(E),
+                        features_M, lpr, bf16, out, pm, status, s))) {
+    const int grid = grid_for(B, 4, s);
+    if (bf16)
+      hipLaunchKernelGGL(hybrid_rows_generic_pool<true>, dim3(grid), dim3(256), 0, s,
+                         idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
+                         time_begin, time_end, reinterpret_cast<const char*>(E),
+                         features_M, k, out, pm, status);
+    else
+      hipLaunchKernelGGL(hybrid_rows_generic_pool<false>, dim3(grid), dim3(256), 0, s,
+                         idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
+                         time_begin, time_end, reinterpret_cast<const char*>(E),
+                         features_M, k, out, pm, status);
+  }
+  return (int)hipGetLastError();
 }
 
 extern "C" const char* hhfm_error_string(int code) {

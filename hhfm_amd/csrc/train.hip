@@ -41,6 +41,7 @@
 
 #include "dropout.h"
 #include "gemm_mfma.h"
+#include "hhfm_pool.h"
 
 namespace hhfm {
 
@@ -198,6 +199,107 @@ __global__ __launch_bounds__(256) void hhfm_train_rows(
       atomicAdd(dE + iu * k + c, dh);
       for (int j = c0; j < c1; ++j) atomicAdd(dE + (int64_t)clamp_id(x[j], M) * k + c, dh);
       for (int j = t0; j < t1; ++j) atomicAdd(dE + (int64_t)clamp_id(x[j], M) * k + c, dh);
+    }
+    if (l == 0) atomicAdd(scal + kScalDataLoss, -logf(sg));
+  }
+}
+
+// HHFM with MAX / MEAN pooling (include/hhfm.h "Pooling"): hhfm_train_rows
+// with the forward's h from hhfm_pool.h (the scoring kernels' h bit for bit)
+// and TF's pool gradients on the way back: dh_e reaches the stack members
+// through the final pool and the context / time rows through theirs
+// (pool_grad: max shares between the values equal to the maximum at that
+// element, mean divides by the count).  The BPR part — reduce_max over the
+// negatives with ties split, g, gt — and the loss are hhfm_train_rows's.
+__global__ __launch_bounds__(256) void hhfm_train_rows_pool(
+    const int32_t* __restrict__ X, const int32_t* __restrict__ Neg, int64_t B, int ncols,
+    int c0, int c1, int t0, int t1, int NG, const float* __restrict__ E, int64_t M, int k,
+    PoolModes pm, float* __restrict__ dE, float* __restrict__ scal) {
+  const int l = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const int nc = c1 > c0 ? c1 - c0 : 0, ntm = t1 > t0 ? t1 - t0 : 0;
+  const int members = 1 + (nc > 0) + (ntm > 0);
+  for (int64_t b = wave; b < B; b += nwave) {
+    const int32_t* x = X + b * ncols;
+    const int32_t* ng = Neg + b * NG;
+    const int64_t iu = clamp_id(x[0], M), ii = clamp_id(x[1], M);
+    auto row = [&](int j, int c) { return E[(int64_t)clamp_id(x[j], M) * k + c]; };
+    // h at element c; cv / tv: the pools' values (a max pool's value is its maximum)
+    auto hval = [&](int c, float& cv, float& tv) {
+      cv = pool_identity(pm.ctx);
+      tv = pool_identity(pm.tim);
+      for (int j = c0; j < c1; ++j) cv = pool_step(pm.ctx, cv, row(j, c));
+      for (int j = t0; j < t1; ++j) tv = pool_step(pm.tim, tv, row(j, c));
+      cv = pool_finish(pm.ctx, cv, nc);
+      tv = pool_finish(pm.tim, tv, ntm);
+      return pool_h(E[iu * k + c], cv, nc, tv, ntm, pm.fin);
+    };
+    auto h_only = [&](int c) {
+      float cv, tv;
+      return hval(c, cv, tv);
+    };
+    float pos = 0.f;
+    for (int c = l; c < k; c += kWave) pos += h_only(c) * E[ii * k + c];
+    pos = group_sum<kWave>(pos);                        // PositiveFeadback  :171
+    float negv[kMaxNeg];
+    float mx = -__builtin_huge_valf();
+#pragma unroll
+    for (int j = 0; j < kMaxNeg; ++j) {
+      negv[j] = -__builtin_huge_valf();
+      if (j < NG) {
+        float v = 0.f;
+        const int64_t in = clamp_id(ng[j], M);
+        for (int c = l; c < k; c += kWave) v += h_only(c) * E[in * k + c];
+        v = group_sum<kWave>(v);
+        negv[j] = v;
+        mx = fmaxf(mx, v);
+      }
+    }
+    int nt = 0;
+#pragma unroll
+    for (int j = 0; j < kMaxNeg; ++j) nt += (j < NG && negv[j] == mx);
+    const float z = pos - mx;
+    const float sg = 1.f / (1.f + expf(-z));
+    const float g = sg - 1.f;                           // d(-log σ(z))/dz      :178
+    const float gt = g / (float)nt;
+    for (int c = l; c < k; c += kWave) {
+      float cv, tv;
+      const float h = hval(c, cv, tv);
+      const float u = E[iu * k + c];
+      const float it = E[ii * k + c];
+      float nsum = 0.f;
+#pragma unroll
+      for (int j = 0; j < kMaxNeg; ++j)
+        if (j < NG && negv[j] == mx) nsum += E[(int64_t)clamp_id(ng[j], M) * k + c];
+      const float dh = g * it - gt * nsum;
+      atomicAdd(dE + ii * k + c, g * h);
+#pragma unroll
+      for (int j = 0; j < kMaxNeg; ++j)
+        if (j < NG && negv[j] == mx) atomicAdd(dE + (int64_t)clamp_id(ng[j], M) * k + c, -gt * h);
+      if (members == 1) {                               // h = u under every mode
+        atomicAdd(dE + iu * k + c, dh);
+        continue;
+      }
+      // the final pool: with max, h is the largest member (bit-equal to it)
+      const int feq = (u == h) + (nc > 0 && cv == h) + (ntm > 0 && tv == h);
+      atomicAdd(dE + iu * k + c, pool_grad(pm.fin, dh, u, h, feq, members));
+      if (nc > 0) {
+        const float dc = pool_grad(pm.fin, dh, cv, h, feq, members);
+        int eq = 0;
+        for (int j = c0; j < c1; ++j) eq += row(j, c) == cv;
+        for (int j = c0; j < c1; ++j)
+          atomicAdd(dE + (int64_t)clamp_id(x[j], M) * k + c,
+                    pool_grad(pm.ctx, dc, row(j, c), cv, eq, nc));
+      }
+      if (ntm > 0) {
+        const float dt = pool_grad(pm.fin, dh, tv, h, feq, members);
+        int eq = 0;
+        for (int j = t0; j < t1; ++j) eq += row(j, c) == tv;
+        for (int j = t0; j < t1; ++j)
+          atomicAdd(dE + (int64_t)clamp_id(x[j], M) * k + c,
+                    pool_grad(pm.tim, dt, row(j, c), tv, eq, ntm));
+      }
     }
     if (l == 0) atomicAdd(scal + kScalDataLoss, -logf(sg));
   }
@@ -1771,7 +1873,10 @@ static int hhfm_train_step_impl(const int32_t* X, const int32_t* Neg, int64_t B,
                                 int32_t time_end, int32_t NG, float* E, int64_t features_M,
                                 int32_t k, float lr, float lam, int32_t optimizer, float* accE,
                                 void* workspace, size_t ws_bytes, bool det, void* scratch,
-                                size_t scratch_bytes, float* loss, void* stream) {
+                                size_t scratch_bytes, float* loss, void* stream,
+                                int32_t pooling = 0) {
+  PoolModes pm;
+  if (!pooling_unpack(pooling, pm) || (pooling != 0 && det)) return HHFM_EINVAL;
   if (B < 0 || ncols < 2 || NG < 1 || k < 1 || features_M < 1) return HHFM_EINVAL;
   if (NG > kMaxNeg) return HHFM_EUNSUPPORTED;
   if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
@@ -1791,7 +1896,11 @@ static int hhfm_train_step_impl(const int32_t* X, const int32_t* Neg, int64_t B,
   float* ws = reinterpret_cast<float*>(workspace);
   float* scal = ws + p.off_scal;
   char* sc = reinterpret_cast<char*>(scratch);
-  if (B > 0 && !det) {
+  if (B > 0 && pooling != 0) {
+    hipLaunchKernelGGL(hhfm_train_rows_pool, dim3(grid_for_n(B * 64)), dim3(256), 0, st, X, Neg,
+                       B, ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E, features_M, k,
+                       pm, ws + p.off_dE, scal);
+  } else if (B > 0 && !det) {
     hipLaunchKernelGGL(hhfm_train_rows, dim3(grid_for_n(B * 64)), dim3(256), 0, st, X, Neg, B,
                        ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E, features_M, k,
                        ws + p.off_dE, scal);
@@ -1825,6 +1934,18 @@ extern "C" int hhfm_hhfm_train_step(const int32_t* X, const int32_t* Neg, int64_
   return hhfm_train_step_impl(X, Neg, B, ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E,
                               features_M, k, lr, lam, optimizer, accE, workspace, ws_bytes, false,
                               nullptr, 0, loss, stream);
+}
+
+extern "C" int hhfm_hhfm_train_step_pool(const int32_t* X, const int32_t* Neg, int64_t B,
+                                         int32_t ncols, int32_t ctx_begin, int32_t ctx_end,
+                                         int32_t time_begin, int32_t time_end, int32_t NG,
+                                         float* E, int64_t features_M, int32_t k, float lr,
+                                         float lam, int32_t optimizer, float* accE,
+                                         void* workspace, size_t ws_bytes, int32_t pooling,
+                                         float* loss, void* stream) {
+  return hhfm_train_step_impl(X, Neg, B, ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E,
+                              features_M, k, lr, lam, optimizer, accE, workspace, ws_bytes, false,
+                              nullptr, 0, loss, stream, pooling);
 }
 
 extern "C" int hhfm_hhfm_train_step_det(const int32_t* X, const int32_t* Neg, int64_t B,

@@ -6,6 +6,7 @@ function launches a hand-written gfx950 kernel from ``libhhfm.so`` on
 """
 from __future__ import annotations
 
+import numbers
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -35,6 +36,34 @@ PLAN_WIDE_2X4 = 2 << 11
 PLAN_WIDE_1X4 = 3 << 11
 PLAN_STORE = 1 << 13      # small catalog: score matrix + dense top-K (not the fused kernel)
 PLAN_FUSED = 1 << 14      # small catalog: the fused score-and-select kernel at any query count
+
+
+# HHFM pooling modes (include/hhfm.h enum hhfm_pool): how the context rows, the
+# time rows and the stack {user, context pool, time pool} are reduced
+POOL_SUM = 0
+POOL_MAX = 1
+POOL_MEAN = 2
+_POOL_NAMES = {"sum": POOL_SUM, "max": POOL_MAX, "mean": POOL_MEAN}
+
+
+def pool_mode(x) -> int:
+    """One pooling mode: "sum" / "max" / "mean" or a POOL_* value."""
+    if isinstance(x, str) and x in _POOL_NAMES:
+        return _POOL_NAMES[x]
+    if isinstance(x, numbers.Integral) and not isinstance(x, bool) and int(x) in _POOL_NAMES.values():
+        return int(x)
+    raise ValueError(f"pooling mode must be 'sum', 'max', 'mean' or a POOL_* value, got {x!r}")
+
+
+def pooling_word(pooling) -> int:
+    """HHFM_POOLING(ctx, time, final) of a (ctx, time, final) triple; None is
+    (sum, sum, sum) = 0."""
+    if pooling is None:
+        return 0
+    if isinstance(pooling, (str, numbers.Integral)) or len(pooling) != 3:
+        raise ValueError(f"pooling must be a (ctx, time, final) triple, got {pooling!r}")
+    c, t, f = (pool_mode(x) for x in pooling)
+    return c | t << 4 | f << 8
 
 
 def _dtype_code(t: torch.Tensor) -> int:
@@ -137,14 +166,24 @@ def hybrid_score_rows(idx: torch.Tensor, E: torch.Tensor, user_col: int = 0,
                       item_col: int = 1, ctx: Tuple[int, int] = (0, 0),
                       time: Tuple[int, int] = (0, 0),
                       out: Optional[torch.Tensor] = None,
-                      status: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """OUR.PositiveFeadback (OurModel7.py:105-171) for rows ``idx`` -> [B]."""
+                      status: Optional[torch.Tensor] = None,
+                      pooling=None) -> torch.Tensor:
+    """OUR.PositiveFeadback (OurModel7.py:105-171) for rows ``idx`` -> [B].
+    ``pooling``: (ctx, time, final) modes, "sum" / "max" / "mean" or POOL_*
+    (OurModel7.py:14-19 Pooling1C / 1T / 1F); None is sum pooling."""
     _idx(idx, "idx")
     dev = _need_cuda(idx, E, out)
     B, ncols = idx.shape
     M, k = E.shape
+    word = pooling_word(pooling)
     if out is None:
         out = torch.empty(B, dtype=torch.float32, device=dev)
+    if pooling is not None:
+        native().hybrid_score_rows_pool(idx.data_ptr(), B, ncols, user_col, item_col,
+                                        ctx[0], ctx[1], time[0], time[1], E.data_ptr(), M, k,
+                                        _dtype_code(E), out.data_ptr(), word,
+                                        _status_ptr(status), _stream(dev))
+        return out
     native().hybrid_score_rows(idx.data_ptr(), B, ncols, user_col, item_col,
                                ctx[0], ctx[1], time[0], time[1], E.data_ptr(), M, k,
                                _dtype_code(E), out.data_ptr(), _status_ptr(status),
@@ -184,21 +223,31 @@ def catalog_topk(qidx: torch.Tensor, E: torch.Tensor, mode: int, K: int,
                  item_row_begin: int, item_count: int, global_item_base: int = 0,
                  w: Optional[torch.Tensor] = None, user_col: int = 0,
                  ctx: Tuple[int, int] = (0, 0), time: Tuple[int, int] = (0, 0),
-                 status: Optional[torch.Tensor] = None, plan: int = 0
+                 status: Optional[torch.Tensor] = None, plan: int = 0, pooling=None
                  ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Full-catalog score + top-K (FM.topk FM.py:172-198, OUR.topk
     OurModel7.py:229-307). Returns (scores float32 [B,K], ids int32 [B,K]).
     ``plan``: PLAN_* flags (PLAN_EXACT_FP32, _NO_SEED, _NO_RING, _RING_ALT,
-    _GEMM, _ONE_WAVE)."""
+    _GEMM, _ONE_WAVE).  ``pooling``: as in :func:`hybrid_score_rows`
+    (MODE_HHFM only)."""
     _idx(qidx, "qidx")
     dev = _need_cuda(qidx, E, w)
     B, ncols = qidx.shape
     M, k = E.shape
+    word = pooling_word(pooling)
     nat = native()
     st = _stream(dev)
     ws = _catalog_workspace(dev, st, nat.catalog_topk_workspace(B, item_count, k, K))
     top_s = torch.empty(B, K, dtype=torch.float32, device=dev)
     top_i = torch.empty(B, K, dtype=torch.int32, device=dev)
+    if pooling is not None:
+        nat.catalog_topk_pool(qidx.data_ptr(), B, ncols, mode, user_col, ctx[0], ctx[1],
+                              time[0], time[1], E.data_ptr(), M, k, _dtype_code(E),
+                              0 if w is None else w.data_ptr(), item_row_begin, item_count,
+                              global_item_base, K, top_s.data_ptr(), top_i.data_ptr(),
+                              ws.data_ptr(), ws.numel(), int(plan), word,
+                              _status_ptr(status), st)
+        return top_s, top_i
     nat.catalog_topk(qidx.data_ptr(), B, ncols, mode, user_col, ctx[0], ctx[1],
                      time[0], time[1], E.data_ptr(), M, k, _dtype_code(E),
                      0 if w is None else w.data_ptr(), item_row_begin, item_count,

@@ -156,6 +156,10 @@ def fm_partial_fit(model, data) -> float:
 def hhfm_partial_fit(model, data) -> float:
     """OUR.partial_fit (OurModel7.py:219-228): data X [B,2], Y [B,NG] negatives,
     F1 ctx columns, F2 time columns."""
+    pooling = getattr(model, "pooling", None)
+    if pooling is not None and getattr(model, "deterministic", False):
+        raise NotImplementedError("deterministic=True has no MAX / MEAN pooled step yet "
+                                  "(hhfm_hhfm_train_step_det is sum pooling only)")
     opt = _opt_code(model)
     W = model.weights
     st = _state(model, ["feature_embeddings"], opt, fixed_ws=True)
@@ -175,7 +179,9 @@ def hhfm_partial_fit(model, data) -> float:
             float(model.lamda_bilinear), opt, st["feature_embeddings"].data_ptr(),
             st["ws"].data_ptr(), st["ws"].numel())
     tail = (st["loss"].data_ptr(), ops._stream(model.device))
-    if getattr(model, "deterministic", False):
+    if pooling is not None:
+        native().hhfm_train_step_pool(*args, ops.pooling_word(pooling), *tail)
+    elif getattr(model, "deterministic", False):
         occ = 2 + NG + (ctx[1] - ctx[0]) + (tim[1] - tim[0])   # item, negatives, user, fields
         sc = _det_scratch(model, st, B, occ)
         native().hhfm_train_step_det(*args, sc.data_ptr(), sc.numel(), *tail)

@@ -164,6 +164,45 @@ int hhfm_hybrid_score_rows_ex(const int32_t* idx, int64_t B, int32_t ncols,
                               void* stream);
 
 /* ------------------------------------------------------------------------
+ * Pooling — MAX and MEAN beside SUM for the three live pools of the reference
+ * (OurModel7.py:14-19: Pooling1C over the context rows :124 / :255, Pooling1T
+ * over the time rows :141 / :267, Pooling1F over the stack {user, context
+ * pool, time pool} :168 / :292; its Pooling2* results are never used).
+ * The *_pool entry points below are pure additions: every earlier entry point
+ * keeps its signature and behaviour, so HHFM_ABI_VERSION stays 6.
+ *
+ * `pooling` packs the three modes, ctx | time << 4 | final << 8
+ * (HHFM_POOLING); all 27 triples are legal runtime values, any other bit or
+ * mode value is HHFM_EINVAL.  pooling == 0 (sum, sum, sum) runs the very
+ * kernels the unpooled entry points run: the same bits.
+ * Per element e, in fp32 (nc context rows, nt time rows, in column order):
+ *   context pool  sum ((r0 + r1) + ...); max the largest value (the
+ *                 accumulator starts from the first row, never from 0); mean
+ *                 that sum, then one fp32 division by (float)nc
+ *   time pool     the same over the nt time rows
+ *   stack         user, then the context pool if nc > 0, then the time pool
+ *                 if nt > 0
+ *   h             the final pool over the stack in that order: sum
+ *                 (u + c) + t, max the largest member, mean the sum form
+ *                 divided by the number of members; a single member: h = u
+ *   score         Σ_e h_e · item_e, as in H1 / H2
+ * (csrc/hhfm_pool.h is the one device implementation; numpy restatement in
+ * tests/hhfm_pool_ref.py.)
+ * hhfm_hhfm_train_step_det has no pooled form yet.
+ * ---------------------------------------------------------------------- */
+enum hhfm_pool { HHFM_POOL_SUM = 0, HHFM_POOL_MAX = 1, HHFM_POOL_MEAN = 2 };
+#define HHFM_POOLING(ctx, time, final) ((ctx) | (time) << 4 | (final) << 8)
+
+/* H1 with pooling (the arguments of hhfm_hybrid_score_rows_ex, then `pooling`). */
+int hhfm_hybrid_score_rows_pool(const int32_t* idx, int64_t B, int32_t ncols,
+                                int32_t user_col, int32_t item_col,
+                                int32_t ctx_begin, int32_t ctx_end,
+                                int32_t time_begin, int32_t time_end,
+                                const void* E, int64_t features_M, int32_t k,
+                                int32_t dtype, float* out, int32_t pooling,
+                                int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------
  * M2/H2 — full-catalog score + fused top-K (replaces FM.topk, FM.py:172-198,
  * and OUR.topk, OurModel7.py:229-307: broadcast multiply [B,N,k] +
  * reduce_sum + tf.nn.top_k), without materialising the [B,N] score matrix.
@@ -209,6 +248,22 @@ int hhfm_catalog_topk_ex(const int32_t* qidx, int64_t B, int32_t ncols,
                          int32_t item_count, int32_t global_item_base, int32_t K,
                          float* top_score, int32_t* top_idx, void* workspace,
                          size_t ws_bytes, int32_t plan, int32_t* status, void* stream);
+/* Same, with `pooling` ("Pooling" above) for HHFM_MODE_HHFM: the query vector
+ * h is the pooled one, everything after it (the MFMA kernels, the seed, the
+ * ring, the merges) is unchanged.  HHFM_MODE_FM with pooling != 0 is
+ * HHFM_EINVAL.  The workspace query and the plan rules are unchanged: a
+ * small catalog takes the fused kernel (its POOL form: the same h in its
+ * step 0) where the sum form takes it, and HHFM_PLAN_STORE / _FUSED / _GEMM
+ * mean what they mean there. */
+int hhfm_catalog_topk_pool(const int32_t* qidx, int64_t B, int32_t ncols,
+                           int32_t mode, int32_t user_col, int32_t ctx_begin,
+                           int32_t ctx_end, int32_t time_begin, int32_t time_end,
+                           const void* E, int64_t features_M, int32_t k,
+                           int32_t dtype, const float* w, int32_t item_row_begin,
+                           int32_t item_count, int32_t global_item_base, int32_t K,
+                           float* top_score, int32_t* top_idx, void* workspace,
+                           size_t ws_bytes, int32_t plan, int32_t pooling,
+                           int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------------
  * Top-K merge of R sorted partial lists per query (the item-sharded
@@ -427,6 +482,19 @@ int hhfm_hhfm_train_step(const int32_t* X, const int32_t* Neg, int64_t B, int32_
                          int32_t time_end, int32_t NG, float* E, int64_t features_M,
                          int32_t k, float lr, float lambda_l2, int32_t optimizer, float* accE,
                          void* workspace, size_t ws_bytes, float* loss, void* stream);
+/* hhfm_hhfm_train_step with `pooling` ("Pooling" above): the forward's h is
+ * the pooled one and the backward follows TF's gradients — reduce_max sends
+ * dh_e, divided by the number of values equal to the maximum at element e, to
+ * each of those values (context rows, time rows and stack members alike),
+ * reduce_mean divides by the count.  The BPR part, the optimizer, the l2 term,
+ * the loss and the workspace (hhfm_train_workspace) are hhfm_hhfm_train_step's;
+ * pooling == 0 is that step itself. */
+int hhfm_hhfm_train_step_pool(const int32_t* X, const int32_t* Neg, int64_t B, int32_t ncols,
+                              int32_t ctx_begin, int32_t ctx_end, int32_t time_begin,
+                              int32_t time_end, int32_t NG, float* E, int64_t features_M,
+                              int32_t k, float lr, float lambda_l2, int32_t optimizer,
+                              float* accE, void* workspace, size_t ws_bytes, int32_t pooling,
+                              float* loss, void* stream);
 
 /* Training dropout (`--keep` < 1 of FM.py:42-43, AFM.py:43-44).  The
  * arithmetic and the gradient are tf.nn.dropout's (TF 1.x):

@@ -8,8 +8,11 @@ step (NG = 10) and the deterministic steps (FM at keep 1 and 0.5, HHFM) next
 to their default ones, and FM at B = 32,773 with one id in every row (the
 longest serial walk of the segment pass), default and deterministic; --dfm adds
 the default DeepFM step (150/200/150), and --det, on a build that has them,
-also the deterministic AFM (keep 1 and [0.8, 0.5]) and DeepFM steps.
-usage: python scripts/train_step_time.py LIBDIR TAG [--drop] [--det] [--dfm]"""
+also the deterministic AFM (keep 1 and [0.8, 0.5]) and DeepFM steps; --pooling
+adds the default HHFM step (NG = 10) and, on a build that has
+hhfm_train_step_pool, the (max, max, max) and (mean, mean, mean) pooled steps
+alternated with it (two rounds).
+usage: python scripts/train_step_time.py LIBDIR TAG [--drop] [--det] [--dfm] [--pooling]"""
 import importlib.machinery
 import importlib.util
 import json
@@ -153,6 +156,31 @@ if det:
     Xh, yh = dev(Xh), dev(rng.choice([1.0, -1.0], Bh).astype(np.float32))
     res["fm_hot32773_us"] = timed(fm_step(Xh, yh, Bh, 1.0, None), reps=3, n=10)
     res["fm_det_hot32773_us"] = timed(fm_step(Xh, yh, Bh, 1.0, scratch(Bh, F)), reps=3, n=10)
+
+if "--pooling" in sys.argv:
+    NGp = 10
+    Negp = dev(np.random.default_rng(1).integers(nu, nu + ni, (B, NGp)).astype(np.int32))
+    (pE,), (pacc,) = params([(M, k)], [0.1])
+    pws = torch.zeros(nat.train_workspace(M, k), dtype=torch.uint8, device="cuda")
+
+    def hhfm_pool_step(word):
+        """The default HHFM step (word None) or the pooled one (HHFM_POOLING word)."""
+        def fn():
+            args = (X.data_ptr(), Negp.data_ptr(), B, F, 2, F, 0, 0, NGp, pE.data_ptr(), M, k, 0.1,
+                    0.01, 0, pacc.data_ptr(), pws.data_ptr(), pws.numel())
+            if word is None:
+                nat.hhfm_train_step(*args, loss.data_ptr(), st)
+            else:
+                nat.hhfm_train_step_pool(*args, word, loss.data_ptr(), st)
+        return fn
+
+    cases = [("hhfm_sum_ng10_us", None)]
+    if hasattr(nat, "hhfm_train_step_pool"):
+        cases += [("hhfm_pool_max_ng10_us", 1 | 1 << 4 | 1 << 8),
+                  ("hhfm_pool_mean_ng10_us", 2 | 2 << 4 | 2 << 8)]
+    for rnd in (1, 2):
+        for name, word in cases:
+            res[f"{name}_round{rnd}"] = timed(hhfm_pool_step(word))
 
 if det or "--dfm" in sys.argv:
     # DeepFM 150/200/150 (DFM.py:256), default step; with --det, on a build that

@@ -367,14 +367,19 @@ def dfm_catalog_topk(qidx: torch.Tensor, E: torch.Tensor, w: torch.Tensor, Wt, b
 
 def topk_dense(scores: torch.Tensor, K: int, global_item_base: int = 0, plan: int = 0):
     """tf.nn.top_k over a device score matrix [B, N] (K <= 64); ``plan``
-    PLAN_ONE_WAVE keeps one wave per query."""
-    _need_cuda(scores)
+    PLAN_ONE_WAVE keeps one wave per query.  The rows may be a column slice of
+    a wider matrix (unit column stride, leading dimension >= N)."""
     if scores.dtype != torch.float32 or scores.dim() != 2:
         raise TypeError("scores must be float32 [B, N]")
     B, N = scores.shape
+    if not scores.is_cuda:
+        raise ValueError("hhfm_amd kernels take device (cuda/HIP) tensors")
+    if N > 1 and scores.stride(1) != 1 or B > 1 and scores.stride(0) < N:
+        raise ValueError("scores must have unit column stride and a leading dimension >= N")
     top_s = torch.empty(B, K, dtype=torch.float32, device=scores.device)
     top_i = torch.empty(B, K, dtype=torch.int32, device=scores.device)
-    native().topk_dense(scores.data_ptr(), B, N, scores.stride(0), K, global_item_base,
+    native().topk_dense(scores.data_ptr(), B, N, scores.stride(0) if B > 1 else N, K,
+                        global_item_base,
                         top_s.data_ptr(), top_i.data_ptr(), int(plan), _stream(scores.device))
     return top_s, top_i
 

@@ -220,6 +220,10 @@ int hhfm_hybrid_score_rows_pool(const int32_t* idx, int64_t B, int32_t ncols,
  *            order >= 2^-16 kept, fp32 accumulation: ~1e-7 relative to a
  *            k-ordered fp32 chain); plan HHFM_PLAN_EXACT_FP32 (the _ex form)
  *            selects the fp32-MFMA kernels (the k-ordered fmaf chain).
+ *   score range: the streaming path without a threshold seed starts its
+ *            per-query threshold hint at about -3.39e38 (the workspace words
+ *            are filled with byte 0x80), so catalog scores are assumed finite
+ *            and above that value; +-inf or NaN table values are unsupported.
  * Workspace: query `hhfm_catalog_topk_workspace` with the same sizes (it
  * covers every plan).  Its first HHFM_CATALOG_WS_ZERO bytes must be zero
  * before the first call (the small-catalog kernel's per-call arrival

@@ -53,9 +53,9 @@ class DeepFM(ScoringModel):
         assert use_fm or use_deep
         assert loss_type in ["logloss", "mse"], \
             "loss_type can be either 'logloss' for classification task or 'mse' for regression task"
-        if not (use_fm and use_deep and loss_type == "mse"):
-            raise NotImplementedError("the scoring kernels implement the reference setting "
-                                      "use_fm=use_deep=True, loss_type='mse' (DFM.py:255-257)")
+        # the head word of the scoring and training entry points (include/hhfm.h
+        # "DeepFM heads"); the reference default keeps the entry points without one
+        self.head = ops.dfm_head_word(use_fm, use_deep, loss_type)
         self.n_user = n_user
         self.n_item = n_item
         self.feature_size = feature_size
@@ -101,7 +101,8 @@ class DeepFM(ScoringModel):
             W[f"bias_{i}"] = torch.from_numpy(
                 rng.normal(0, glorot, (1, n)).astype(np.float32)).to(self.device)
             fan_in = n
-        inp = F + k + self.deep_layers[-1]
+        # DFM.py:199-204: the projection sees the present parts only
+        inp = (F + k if self.use_fm else 0) + (self.deep_layers[-1] if self.use_deep else 0)
         glorot = np.sqrt(2.0 / (inp + 1))
         W["concat_projection"] = torch.from_numpy(
             rng.normal(0, glorot, (inp, 1)).astype(np.float32)).to(self.device)
@@ -124,20 +125,27 @@ class DeepFM(ScoringModel):
             self._prep = (key, Wt, bs, dims, Wp, float(self.weights["concat_bias"]))
         return self._prep[1:]
 
+    def _head_arg(self):
+        return None if self.head == ops.DFM_HEAD_FM | ops.DFM_HEAD_DEEP else self.head
+
     def score_rows(self, X) -> np.ndarray:
+        """``out`` of DFM.py:137-141: the projection, through the sigmoid under
+        loss_type "logloss"."""
         idx = self._idx(X)
         Wt, bs, dims, Wp, bp = self._prepared()
         out = ops.dfm_forward(idx, self.table, self.weights["feature_bias"].reshape(-1), Wt, bs,
-                              dims, self.mlp_dtype, Wp, bp)
+                              dims, self.mlp_dtype, Wp, bp, head=self._head_arg())
         return self._np_out(out)
 
     def catalog_topk(self, q, begin, count, K):
         """Top-K of items [begin, begin+count) by the DeepFM score of
-        DFM.py:219-231 -> (scores, global item offsets) device tensors [B, K]."""
+        DFM.py:219-231 -> (scores, global item offsets) device tensors [B, K].
+        The scores are the pre-sigmoid projection for every loss_type (the
+        ranking is the sigmoid's; item-shard merges stay exact)."""
         Wt, bs, dims, Wp, bp = self._prepared()
         return ops.dfm_catalog_topk(q, self.table, self.weights["feature_bias"].reshape(-1),
                                     Wt, bs, dims, Wp, bp, 1, self.n_user + begin, count, int(K),
-                                    begin)
+                                    begin, head=self._head_arg())
 
     def topk(self, A, tp):
         _, ids = self.catalog_topk(self._idx(A), 0, self.n_item, tp)

@@ -1608,6 +1608,54 @@ void dfm_project_layer0(const void* E, int64_t M, int k, bool tbf, bool mlp_bf16
   launch_gemm(g, mlp_bf16, 0, st);
 }
 
+// The FM part from the table rows, on its own: base[m] for B rows (k % 4 == 0).
+// The staged kernel when the rows' width admits it (k % 64 == 0, a row within
+// the stage, F within its id buffer), the grid-stride one otherwise — the same
+// bits.  dfm_fused_launch's split forward and the FM head (mlp_gemm.hip) share it.
+void dfm_fm_base_launch(const int32_t* idx, int64_t B, int F, const void* E, int64_t M, int k,
+                        bool tbf, const float* w, const float* Wp, float bp, float* fm_base,
+                        int32_t plan, hipStream_t st) {
+  const int64_t rows_per_block = 256 / 16;
+  int64_t fb = (B + rows_per_block - 1) / rows_per_block;
+  if (fb > 8192) fb = 8192;
+#define HHFM_FMB(KJ)                                                                       \
+  if (tbf)                                                                                 \
+    hipLaunchKernelGGL((dfm_fm_base<true, KJ>), dim3((unsigned)fb), dim3(256), 0, st, idx, B, \
+                       F, E, M, k, w, Wp, bp, fm_base);                                    \
+  else                                                                                     \
+    hipLaunchKernelGGL((dfm_fm_base<false, KJ>), dim3((unsigned)fb), dim3(256), 0, st, idx,   \
+                       B, F, E, M, k, w, Wp, bp, fm_base);
+  const int kj = k % 64 ? 0 : k / 64;
+  const unsigned sblocks = (unsigned)((B + kFmbRows - 1) / kFmbRows);
+#define HHFM_FMBS(KJ)                                                                      \
+  if (tbf)                                                                                 \
+    hipLaunchKernelGGL((dfm_fm_base_st<true, KJ>), dim3(sblocks), dim3(256), 0, st, idx, B, \
+                       F, E, M, k, w, Wp, bp, fm_base);                                    \
+  else                                                                                     \
+    hipLaunchKernelGGL((dfm_fm_base_st<false, KJ>), dim3(sblocks), dim3(256), 0, st, idx,   \
+                       B, F, E, M, k, w, Wp, bp, fm_base);
+  // (a k / 64 without an instantiation runs the generic kernel: 16-B chunks of any k % 4 == 0)
+  const bool kj_inst = kj == 1 || kj == 2 || kj == 4 || kj == 8;
+  if (!(plan & HHFM_PLAN_UNSTAGED) && kj_inst && F <= kFusedMaxF &&
+      k * (tbf ? 2 : 4) <= kFmbStageB) {
+    switch (kj) {
+      case 1: HHFM_FMBS(1) break;
+      case 2: HHFM_FMBS(2) break;
+      case 4: HHFM_FMBS(4) break;
+      default: HHFM_FMBS(8) break;
+    }
+  } else
+  switch (kj) {
+    case 1: HHFM_FMB(1) break;
+    case 2: HHFM_FMB(2) break;
+    case 4: HHFM_FMB(4) break;
+    case 8: HHFM_FMB(8) break;
+    default: HHFM_FMB(0) break;
+  }
+#undef HHFM_FMB
+#undef HHFM_FMBS
+}
+
 // returns false when the shape is outside the fused kernel's envelope.
 // proj != nullptr: the layer-0 products of fields [proj_from, F) come from
 // dfm_project_layer0's workspace (PROJ kernels; the fp32 MLP projects all
@@ -1662,42 +1710,7 @@ bool dfm_fused_launch(const int32_t* idx, int64_t B, int F, const void* E, int64
       // and pays; otherwise from the rows
       if (dfm_fm_pairs(a, tbf, st)) {
       } else {
-        const int64_t rows_per_block = 256 / 16;
-        int64_t fb = (B + rows_per_block - 1) / rows_per_block;
-        if (fb > 8192) fb = 8192;
-#define HHFM_FMB(KJ)                                                                       \
-  if (tbf)                                                                                 \
-    hipLaunchKernelGGL((dfm_fm_base<true, KJ>), dim3((unsigned)fb), dim3(256), 0, st, idx, B, \
-                       F, E, M, k, w, Wp, bp, fm_base);                                    \
-  else                                                                                     \
-    hipLaunchKernelGGL((dfm_fm_base<false, KJ>), dim3((unsigned)fb), dim3(256), 0, st, idx,   \
-                       B, F, E, M, k, w, Wp, bp, fm_base);
-        const int kj = k % 64 ? 0 : k / 64;
-        const unsigned sblocks = (unsigned)((B + kFmbRows - 1) / kFmbRows);
-#define HHFM_FMBS(KJ)                                                                      \
-  if (tbf)                                                                                 \
-    hipLaunchKernelGGL((dfm_fm_base_st<true, KJ>), dim3(sblocks), dim3(256), 0, st, idx, B, \
-                       F, E, M, k, w, Wp, bp, fm_base);                                    \
-  else                                                                                     \
-    hipLaunchKernelGGL((dfm_fm_base_st<false, KJ>), dim3(sblocks), dim3(256), 0, st, idx,   \
-                       B, F, E, M, k, w, Wp, bp, fm_base);
-        if (!(plan & HHFM_PLAN_UNSTAGED) && kj > 0 && k * (tbf ? 2 : 4) <= kFmbStageB) {
-          switch (kj) {
-            case 1: HHFM_FMBS(1) break;
-            case 2: HHFM_FMBS(2) break;
-            case 4: HHFM_FMBS(4) break;
-            default: HHFM_FMBS(8) break;
-          }
-        } else
-        switch (kj) {
-          case 1: HHFM_FMB(1) break;
-          case 2: HHFM_FMB(2) break;
-          case 4: HHFM_FMB(4) break;
-          case 8: HHFM_FMB(8) break;
-          default: HHFM_FMB(0) break;
-        }
-#undef HHFM_FMB
-#undef HHFM_FMBS
+        dfm_fm_base_launch(idx, B, F, E, M, k, tbf, w, Wp, bp, fm_base, plan, st);
       }
       a.fmbase = fm_base;
       a.stage = !(plan & HHFM_PLAN_UNSTAGED);

@@ -3,6 +3,8 @@
 //
 //   hhfm_dfm_forward        replaces DeepFM.out   (Newcode/DFM.py:104-137)
 //   hhfm_dfm_catalog_topk   replaces DeepFM.topk  (Newcode/DFM.py:219-231)
+//   hhfm_dfm_forward_head / hhfm_dfm_catalog_topk_head   the same for the
+//                           FM-only, deep-only and sigmoid heads (DFM.py:131-141)
 //   hhfm_topk_dense         replaces tf.nn.top_k on a materialised [B,N]
 //                           score matrix (DFM.py:230, AFM.py:245)
 //
@@ -44,6 +46,9 @@ const int32_t* dfm_order_rows(const int32_t* idx, int64_t B, int F, int key_fiel
                               void* ws, const int32_t** rows_out, hipStream_t st,
                               const int32_t** franges_out);
 constexpr uint64_t kDfmIdentityPerm = 0xFEDCBA9876543210ull;
+void dfm_fm_base_launch(const int32_t* idx, int64_t B, int F, const void* E, int64_t M, int k,
+                        bool tbf, const float* w, const float* Wp, float bp, float* fm_base,
+                        int32_t plan, hipStream_t st);
 
 // ---------------------------------------------------------------------------
 // FM part of DeepFM and the final reduce
@@ -90,6 +95,20 @@ __global__ __launch_bounds__(256) void dfm_reduce(const float* __restrict__ base
   float s = 0.f;
   for (int t = 0; t < nt; ++t) s += partial[m * nt + t];
   out[m] = base[m] + s;
+}
+
+// DeepFM heads (include/hhfm.h): out = 1/(1 + expf(−z)) over the forward's z, in place
+__global__ __launch_bounds__(256) void dfm_sigmoid(float* __restrict__ out, int64_t B) {
+  for (int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; m < B;
+       m += (int64_t)gridDim.x * blockDim.x)
+    out[m] = 1.f / (1.f + expf(-out[m]));
+}
+
+// the deep head's projection in the full layout: dst = [0 (nz) | Wp (n)]
+__global__ __launch_bounds__(256) void dfm_zero_prefix(const float* __restrict__ Wp, int nz, int n,
+                                                       float* __restrict__ dst) {
+  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < nz + n; c += gridDim.x * blockDim.x)
+    dst[c] = c < nz ? 0.f : Wp[c - nz];
 }
 
 // rows[b*N + i] = qidx[b] with column item_col replaced by item_row_begin + i
@@ -216,6 +235,35 @@ static bool wt_aligned(int32_t nlayers, const void* const* Wt) {
 static bool proj_mode_ok(int m) {
   return m == HHFM_DFM_PROJ_OFF || m == HHFM_DFM_PROJ_ON || m == HHFM_DFM_PROJ_AUTO ||
          m == HHFM_DFM_PROJ_CTX || m == HHFM_DFM_PROJ_ITEM;
+}
+
+// DeepFM heads: FM or DEEP (or both), SIGMOID optional, nothing else
+static bool head_ok(int32_t head) {
+  return !(head & ~(HHFM_DFM_HEAD_FM | HHFM_DFM_HEAD_DEEP | HHFM_DFM_HEAD_SIGMOID)) &&
+         (head & (HHFM_DFM_HEAD_FM | HHFM_DFM_HEAD_DEEP));
+}
+static bool head_full(int32_t head) {
+  return (head & HHFM_DFM_HEAD_FM) && (head & HHFM_DFM_HEAD_DEEP);
+}
+// bytes after a plan for the deep head's zero-prefixed projection [F + k + d_L]
+static size_t dfm_head_wp_bytes(int F, int k, int nlayers, const int32_t* dims) {
+  return HHFM_DFM_HEAD_WS_EXTRA(F, k, dims[nlayers - 1]);
+}
+static void launch_zero_prefix(const float* Wp, int nz, int n, float* dst, hipStream_t st) {
+  hipLaunchKernelGGL(dfm_zero_prefix, dim3((unsigned)((nz + n + 255) / 256)), dim3(256), 0, st, Wp,
+                     nz, n, dst);
+}
+static void launch_sigmoid(float* out, int64_t B, hipStream_t st) {
+  const int64_t blocks = (B + 255) / 256;
+  hipLaunchKernelGGL(dfm_sigmoid, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0,
+                     st, out, B);
+}
+// the FM head's argument checks (no layer is looked at)
+static int dfm_fm_head_check(int64_t B, int32_t F, int32_t k, int32_t dtype, int64_t features_M) {
+  if (B < 0 || F < 1 || k < 1 || features_M < 1) return HHFM_EINVAL;
+  if (dtype != HHFM_F32 && dtype != HHFM_BF16) return HHFM_EINVAL;
+  if (k % 4) return HHFM_EUNSUPPORTED;   // 16-B (fp32) / 8-B (bf16) column chunks
+  return HHFM_OK;
 }
 
 static int dfm_check(int64_t B, int32_t F, int32_t k, int32_t dtype, int32_t nlayers,
@@ -394,6 +442,54 @@ extern "C" int hhfm_dfm_forward_ex(const int32_t* idx, int64_t B, int32_t F, con
                              plan, reinterpret_cast<hipStream_t>(stream));
 }
 
+// DeepFM heads (include/hhfm.h): FM | DEEP is hhfm_dfm_forward_ex itself; the
+// FM head is the FM part's row kernels alone; the DEEP head the full forward
+// on a zero-prefixed projection.  SIGMOID: one pass over out afterwards.
+extern "C" int hhfm_dfm_forward_head(const int32_t* idx, int64_t B, int32_t F, const void* E,
+                                     int64_t features_M, int32_t k, int32_t dtype,
+                                     const float* w, int32_t nlayers, const int32_t* layer_dims,
+                                     const void* const* Wt, const float* const* bias,
+                                     int32_t mlp_dtype, const float* Wp, float bp, float* out,
+                                     int32_t proj_mode, int32_t plan, void* workspace,
+                                     size_t ws_bytes, void* stream, int32_t head) {
+  if (!head_ok(head)) return HHFM_EINVAL;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  int rc;
+  if (head_full(head)) {
+    rc = hhfm_dfm_forward_ex(idx, B, F, E, features_M, k, dtype, w, nlayers, layer_dims, Wt, bias,
+                             mlp_dtype, Wp, bp, out, proj_mode, plan, workspace, ws_bytes, stream);
+  } else if (head & HHFM_DFM_HEAD_FM) {
+    if (!proj_mode_ok(proj_mode) || !plan_ok(plan)) return HHFM_EINVAL;
+    rc = dfm_fm_head_check(B, F, k, dtype, features_M);
+    if (rc || B == 0) return rc;
+    if (!idx || !E || !w || !Wp || !out) return HHFM_EINVAL;
+    dfm_fm_base_launch(idx, B, F, E, features_M, k, dtype == HHFM_BF16, w, Wp, bp, out,
+                       HHFM_PLAN_DEFAULT, st);
+    rc = (int)hipGetLastError();
+  } else {
+    if (!proj_mode_ok(proj_mode) || !plan_ok(plan)) return HHFM_EINVAL;
+    rc = dfm_forward_args(idx, B, F, E, features_M, k, dtype, w, nlayers, layer_dims, Wt, bias,
+                          mlp_dtype, Wp, out);
+    if (rc != 1) return rc;
+    if (!wt_aligned(nlayers, Wt)) proj_mode = HHFM_DFM_PROJ_OFF;
+    const DfmPlan p = dfm_plan(B, nlayers, layer_dims, mlp_dtype, F, k, features_M, B, proj_mode,
+                               1, true, plan);
+    if (!workspace || ws_bytes < p.total + dfm_head_wp_bytes(F, k, nlayers, layer_dims))
+      return HHFM_EWORKSPACE;
+    char* ws = reinterpret_cast<char*>(workspace);
+    float* Wpz = reinterpret_cast<float*>(ws + p.total);
+    launch_zero_prefix(Wp, F + k, layer_dims[nlayers - 1], Wpz, st);
+    rc = dfm_forward_planned(idx, B, F, E, features_M, k, dtype, w, nlayers, layer_dims, Wt, bias,
+                             mlp_dtype, Wpz, bp, out, ws, p, plan, st);
+  }
+  if (rc) return rc;
+  if ((head & HHFM_DFM_HEAD_SIGMOID) && B > 0) {
+    launch_sigmoid(out, B, st);
+    rc = (int)hipGetLastError();
+  }
+  return rc;
+}
+
 // D2: chunk_rows bounds the rows (queries x items) scored per forward pass.
 static int64_t dfm_cat_qchunk(int64_t B, int32_t N, int64_t chunk_rows) {
   int64_t qc = chunk_rows / N;
@@ -443,7 +539,7 @@ static int dfm_catalog_run(const int32_t* qidx, int64_t B, int32_t F, int32_t it
                            int32_t item_count, int32_t global_item_base, int32_t K,
                            int64_t chunk_rows, float* top_score, int32_t* top_idx,
                            void* workspace, size_t ws_bytes, int proj_mode, int32_t plan,
-                           void* stream) {
+                           void* stream, bool deep_only = false) {
   int rc = dfm_check(B, F, k, dtype, nlayers, layer_dims, mlp_dtype);
   if (rc) return rc;
   if (item_col < 0 || item_col >= F || item_count < 1 || item_row_begin < 0 ||
@@ -466,11 +562,19 @@ static int dfm_catalog_run(const int32_t* qidx, int64_t B, int32_t F, int32_t it
     p = dfm_plan(rows, nlayers, layer_dims, mlp_dtype, F, k, features_M,
                  B * (int64_t)item_count, proj_mode, item_col, false, plan);
   }
-  if (!workspace || ws_bytes < dfm_cat_bytes(p, rows, F)) return HHFM_EWORKSPACE;
+  const size_t cat_bytes = dfm_cat_bytes(p, rows, F);
+  if (!workspace ||
+      ws_bytes < cat_bytes + (deep_only ? dfm_head_wp_bytes(F, k, nlayers, layer_dims) : 0))
+    return HHFM_EWORKSPACE;
   char* ws = reinterpret_cast<char*>(workspace);
   int32_t* rbuf = reinterpret_cast<int32_t*>(ws + p.total);
   float* sc = reinterpret_cast<float*>(ws + p.total + al256((size_t)rows * F * 4));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (deep_only) {   // the deep head: the projection in the full layout, zeros in front
+    float* Wpz = reinterpret_cast<float*>(ws + cat_bytes);
+    launch_zero_prefix(Wp, F + k, layer_dims[nlayers - 1], Wpz, st);
+    Wp = Wpz;
+  }
   const void* proj = nullptr;
   if (p.proj) {   // once per call: every query chunk reuses it
     dfm_project_layer0(E, features_M, k, dtype == HHFM_BF16, mlp_dtype == HHFM_BF16, F,
@@ -529,6 +633,67 @@ extern "C" int hhfm_dfm_catalog_topk_ex(const int32_t* qidx, int64_t B, int32_t 
                          Wt, bias, mlp_dtype, Wp, bp, item_row_begin, item_count,
                          global_item_base, K, chunk_rows, top_score, top_idx, workspace,
                          ws_bytes, proj_mode, plan, stream);
+}
+
+// The FM head's catalog: rows tiled as above, scored by the FM part's row
+// kernels, dense top-K.  Workspace: [rows F ids][rows scores] from offset 0
+// (within every hhfm_dfm_catalog_topk_workspace* size of the same chunk_rows).
+static int dfm_catalog_fm(const int32_t* qidx, int64_t B, int32_t F, int32_t item_col,
+                          const void* E, int64_t features_M, int32_t k, int32_t dtype,
+                          const float* w, const float* Wp, float bp, int32_t item_row_begin,
+                          int32_t item_count, int32_t global_item_base, int32_t K,
+                          int64_t chunk_rows, float* top_score, int32_t* top_idx,
+                          void* workspace, size_t ws_bytes, int32_t plan, void* stream) {
+  int rc = dfm_fm_head_check(B, F, k, dtype, features_M);
+  if (rc) return rc;
+  if (item_col < 0 || item_col >= F || item_count < 1 || item_row_begin < 0 ||
+      (int64_t)item_row_begin + item_count > features_M || chunk_rows < 1)
+    return HHFM_EINVAL;
+  if (K < 1 || K > item_count) return HHFM_EINVAL;
+  if (K > 64) return HHFM_EUNSUPPORTED;
+  if (B == 0) return HHFM_OK;
+  if (!qidx || !E || !w || !Wp || !top_score || !top_idx) return HHFM_EINVAL;
+  const int64_t qc = dfm_cat_qchunk(B, item_count, chunk_rows);
+  const int64_t rows = qc * item_count;
+  const size_t off_sc = al256((size_t)rows * F * 4);
+  if (!workspace || ws_bytes < off_sc + al256((size_t)rows * 4)) return HHFM_EWORKSPACE;
+  char* ws = reinterpret_cast<char*>(workspace);
+  int32_t* rbuf = reinterpret_cast<int32_t*>(ws);
+  float* sc = reinterpret_cast<float*>(ws + off_sc);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  for (int64_t b0 = 0; b0 < B; b0 += qc) {
+    const int64_t nb = (B - b0) < qc ? (B - b0) : qc;
+    const int64_t nrows = nb * item_count;
+    int64_t blocks = (nrows * F + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(dfm_build_rows, dim3((unsigned)blocks), dim3(256), 0, st, qidx + b0 * F,
+                       nb, F, item_col, item_row_begin, item_count, rbuf);
+    dfm_fm_base_launch(rbuf, nrows, F, E, features_M, k, dtype == HHFM_BF16, w, Wp, bp, sc,
+                       HHFM_PLAN_DEFAULT, st);
+    launch_topk_dense(sc, nb, item_count, item_count, K, global_item_base, top_score + b0 * K,
+                      top_idx + b0 * K, st, (plan & HHFM_PLAN_ONE_WAVE) != 0);
+  }
+  return (int)hipGetLastError();
+}
+
+// DeepFM heads: ranks by z and returns z whatever the SIGMOID bit (monotone)
+extern "C" int hhfm_dfm_catalog_topk_head(
+    const int32_t* qidx, int64_t B, int32_t F, int32_t item_col, const void* E,
+    int64_t features_M, int32_t k, int32_t dtype, const float* w, int32_t nlayers,
+    const int32_t* layer_dims, const void* const* Wt, const float* const* bias,
+    int32_t mlp_dtype, const float* Wp, float bp, int32_t item_row_begin, int32_t item_count,
+    int32_t global_item_base, int32_t K, int64_t chunk_rows, float* top_score, int32_t* top_idx,
+    int32_t proj_mode, int32_t plan, void* workspace, size_t ws_bytes, void* stream,
+    int32_t head) {
+  if (!head_ok(head) || !proj_mode_ok(proj_mode) || !plan_ok(plan)) return HHFM_EINVAL;
+  if (!(head & HHFM_DFM_HEAD_DEEP))
+    return dfm_catalog_fm(qidx, B, F, item_col, E, features_M, k, dtype, w, Wp, bp,
+                          item_row_begin, item_count, global_item_base, K, chunk_rows, top_score,
+                          top_idx, workspace, ws_bytes, plan, stream);
+  return dfm_catalog_run(qidx, B, F, item_col, E, features_M, k, dtype, w, nlayers, layer_dims,
+                         Wt, bias, mlp_dtype, Wp, bp, item_row_begin, item_count,
+                         global_item_base, K, chunk_rows, top_score, top_idx, workspace,
+                         ws_bytes, proj_mode, plan, stream, !head_full(head));
 }
 
 extern "C" int hhfm_topk_dense(const float* scores, int64_t B, int32_t N, int64_t ld, int32_t K,

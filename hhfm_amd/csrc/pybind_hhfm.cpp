@@ -696,6 +696,121 @@ PYBIND11_MODULE(_hhfm, m) {
           check(rc, "hhfm_dfm_train_step_det");
         });
 
+  // DeepFM heads (include/hhfm.h): the entry points above plus the head word.
+  // Without HHFM_DFM_HEAD_DEEP the layer lists may be empty.
+  m.def("dfm_forward_head",
+        [](uptr idx, int64_t B, int F, uptr E, int64_t M, int k, int dtype, uptr w,
+           std::vector<int32_t> dims, std::vector<uptr> Wt, std::vector<uptr> bias,
+           int mlp_dtype, uptr Wp, float bp, uptr out, int proj_mode, int plan, uptr ws,
+           size_t ws_bytes, uptr stream, int head) {
+          if (Wt.size() != dims.size() || bias.size() != dims.size())
+            throw py::value_error("dims, Wt and bias must have the same length");
+          std::vector<const void*> W(Wt.size());
+          std::vector<const float*> b(bias.size());
+          for (size_t i = 0; i < W.size(); ++i) {
+            W[i] = P<const void>(Wt[i]);
+            b[i] = P<const float>(bias[i]);
+          }
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_dfm_forward_head(P<const int32_t>(idx), B, F, P<const void>(E), M, k,
+                                       dtype, P<const float>(w), (int)dims.size(),
+                                       dims.empty() ? nullptr : dims.data(),
+                                       W.empty() ? nullptr : W.data(),
+                                       b.empty() ? nullptr : b.data(), mlp_dtype,
+                                       P<const float>(Wp), bp, P<float>(out), proj_mode, plan,
+                                       P<void>(ws), ws_bytes, P<void>(stream), head);
+          }
+          check(rc, "hhfm_dfm_forward_head");
+        });
+
+  m.def("dfm_catalog_topk_head",
+        [](uptr qidx, int64_t B, int F, int item_col, uptr E, int64_t M, int k, int dtype,
+           uptr w, std::vector<int32_t> dims, std::vector<uptr> Wt, std::vector<uptr> bias,
+           int mlp_dtype, uptr Wp, float bp, int item_row_begin, int item_count,
+           int global_item_base, int K, int64_t chunk_rows, uptr top_score, uptr top_idx,
+           int proj_mode, int plan, uptr ws, size_t ws_bytes, uptr stream, int head) {
+          if (Wt.size() != dims.size() || bias.size() != dims.size())
+            throw py::value_error("dims, Wt and bias must have the same length");
+          std::vector<const void*> W(Wt.size());
+          std::vector<const float*> b(bias.size());
+          for (size_t i = 0; i < W.size(); ++i) {
+            W[i] = P<const void>(Wt[i]);
+            b[i] = P<const float>(bias[i]);
+          }
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_dfm_catalog_topk_head(
+                P<const int32_t>(qidx), B, F, item_col, P<const void>(E), M, k, dtype,
+                P<const float>(w), (int)dims.size(), dims.empty() ? nullptr : dims.data(),
+                W.empty() ? nullptr : W.data(), b.empty() ? nullptr : b.data(), mlp_dtype,
+                P<const float>(Wp), bp, item_row_begin, item_count, global_item_base, K,
+                chunk_rows, P<float>(top_score), P<int32_t>(top_idx), proj_mode, plan,
+                P<void>(ws), ws_bytes, P<void>(stream), head);
+          }
+          check(rc, "hhfm_dfm_catalog_topk_head");
+        });
+
+  m.def("dfm_train_step_head",
+        [](uptr idx, uptr y, int64_t B, int F, uptr E, uptr w, int64_t M, int k,
+           std::vector<int32_t> dims, std::vector<uptr> W, std::vector<uptr> bias, uptr Wp,
+           uptr bp, float lr, float lam, int opt, std::vector<uptr> acc, uptr ws,
+           size_t ws_bytes, uptr loss, uptr stream, int head) {
+          if (W.size() != dims.size() || bias.size() != dims.size())
+            throw py::value_error("dims, W and bias must have the same length");
+          if (opt != HHFM_OPT_SGD && acc.size() != 2 * dims.size() + 4)
+            throw py::value_error("acc needs 2 * len(dims) + 4 slot arrays");
+          std::vector<float*> Wv(W.size()), bv(bias.size()), av(acc.size());
+          for (size_t i = 0; i < W.size(); ++i) {
+            Wv[i] = P<float>(W[i]);
+            bv[i] = P<float>(bias[i]);
+          }
+          for (size_t i = 0; i < acc.size(); ++i) av[i] = P<float>(acc[i]);
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_dfm_train_step_head(
+                P<const int32_t>(idx), P<const float>(y), B, F, P<float>(E), P<float>(w), M, k,
+                (int)dims.size(), dims.empty() ? nullptr : dims.data(),
+                Wv.empty() ? nullptr : Wv.data(), bv.empty() ? nullptr : bv.data(), P<float>(Wp),
+                P<float>(bp), lr, lam, opt, av.empty() ? nullptr : av.data(), P<void>(ws),
+                ws_bytes, P<float>(loss), P<void>(stream), head);
+          }
+          check(rc, "hhfm_dfm_train_step_head");
+        });
+
+  m.def("dfm_train_step_head_det",
+        [](uptr idx, uptr y, int64_t B, int F, uptr E, uptr w, int64_t M, int k,
+           std::vector<int32_t> dims, std::vector<uptr> W, std::vector<uptr> bias, uptr Wp,
+           uptr bp, float lr, float lam, int opt, std::vector<uptr> acc, uptr ws,
+           size_t ws_bytes, uptr scratch, size_t scratch_bytes, uptr loss, uptr stream,
+           int head) {
+          if (W.size() != dims.size() || bias.size() != dims.size())
+            throw py::value_error("dims, W and bias must have the same length");
+          if (opt != HHFM_OPT_SGD && acc.size() != 2 * dims.size() + 4)
+            throw py::value_error("acc needs 2 * len(dims) + 4 slot arrays");
+          std::vector<float*> Wv(W.size()), bv(bias.size()), av(acc.size());
+          for (size_t i = 0; i < W.size(); ++i) {
+            Wv[i] = P<float>(W[i]);
+            bv[i] = P<float>(bias[i]);
+          }
+          for (size_t i = 0; i < acc.size(); ++i) av[i] = P<float>(acc[i]);
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_dfm_train_step_head_det(
+                P<const int32_t>(idx), P<const float>(y), B, F, P<float>(E), P<float>(w), M, k,
+                (int)dims.size(), dims.empty() ? nullptr : dims.data(),
+                Wv.empty() ? nullptr : Wv.data(), bv.empty() ? nullptr : bv.data(), P<float>(Wp),
+                P<float>(bp), lr, lam, opt, av.empty() ? nullptr : av.data(), P<void>(ws),
+                ws_bytes, P<void>(scratch), scratch_bytes, P<float>(loss), P<void>(stream),
+                head);
+          }
+          check(rc, "hhfm_dfm_train_step_head_det");
+        });
+
   m.def("topk_dense",
         [](uptr scores, int64_t B, int N, int64_t ld, int K, int base, uptr top_score,
            uptr top_idx, int plan, uptr stream) {

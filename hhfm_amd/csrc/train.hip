@@ -14,6 +14,8 @@
 //   hhfm_*_train_step_det the four steps without float atomics, every sum in a
 //                         fixed order ("Deterministic ... steps" below; AFM's and
 //                         DeepFM's reuse their default kernels under a DET flag)
+//   hhfm_dfm_train_step_head / _head_det  DeepFM's FM-only, deep-only and logloss
+//                         heads (DFM.py:131-152): the DeepFM step under a head word
 //
 // One wave per batch row computes the forward score(s) and scatters the
 // gradient of the row's loss into dense fp32 gradient buffers with float
@@ -1176,6 +1178,13 @@ __global__ __launch_bounds__(256) void row_sums(const float* __restrict__ GT, in
 // DET (hhfm_dfm_train_step_det): no atomics — the partials restart from zero at
 // every row and are stored per row (rowv [B][F+k+dL], for det_columns), the
 // row's loss goes to lossb in double, dw is left to the scatter pass.
+// `head` (include/hhfm.h "DeepFM heads", wave-uniform): the concat columns are
+// the present parts only — [y1 | y2] without DEEP (HL, GL unused), [h_L]
+// without FM (w unread, no dw) — and with SIGMOID z = the projection, p =
+// 1/(1 + expf(−z)), the row's loss is log_loss's l_b (the step divides the sum
+// by B) and g = ((1 − y)/(1 − p + ε) − y/(p + ε))·p·(1 − p)/B.
+constexpr float kLogLossEps = 1e-7f;   // tf.losses.log_loss's default epsilon
+
 template <bool DET>
 __global__ __launch_bounds__(256) void dfm_train_head(
     const int32_t* __restrict__ idx, const float* __restrict__ y, int64_t B, int F,
@@ -1183,10 +1192,13 @@ __global__ __launch_bounds__(256) void dfm_train_head(
     const float* __restrict__ HL, int dL, int64_t ldh, const float* __restrict__ Wp,
     const float* __restrict__ bp, float* __restrict__ GL, float* __restrict__ gvec,
     float* __restrict__ dWp, float* __restrict__ dw, float* __restrict__ scal,
-    float* __restrict__ rowv, double* __restrict__ lossb) {
+    float* __restrict__ rowv, double* __restrict__ lossb, int head) {
   constexpr int NJ = kDfmHeadMaxCols / kWave;
   const int l = threadIdx.x & 63;
-  const int D = F + k + dL;
+  const bool sig = head & HHFM_DFM_HEAD_SIGMOID;
+  const int F1 = head & HHFM_DFM_HEAD_FM ? F : 0;        // y1 columns
+  const int FK = head & HHFM_DFM_HEAD_FM ? F + k : 0;    // y1 and y2 columns
+  const int D = FK + (head & HHFM_DFM_HEAD_DEEP ? dL : 0);
   float part[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) part[j] = 0.f;
@@ -1202,10 +1214,10 @@ __global__ __launch_bounds__(256) void dfm_train_head(
     for (int j = 0; j < NJ; ++j) {
       const int c = l + kWave * j;
       float v = 0.f;
-      if (c < F) {
+      if (c < F1) {
         v = w[clamp_id(x[c], M)];
-      } else if (c < F + k) {
-        const int cc = c - F;
+      } else if (c < FK) {
+        const int cc = c - F1;
         float s = 0.f, q = 0.f;
         for (int f = 0; f < F; ++f) {
           const float e = E[(int64_t)clamp_id(x[f], M) * k + cc];
@@ -1214,20 +1226,28 @@ __global__ __launch_bounds__(256) void dfm_train_head(
         }
         v = 0.5f * (s * s - q);
       } else if (c < D) {
-        v = HL[m * ldh + (c - F - k)];
+        v = HL[m * ldh + (c - FK)];
       }
       cv[j] = v;
       if (c < D) dot = fmaf(v, Wp[c], dot);
     }
     const float out = group_sum<kWave>(dot) + bp[0];
-    const float g = out - y[m];                    // d l2_loss(y − out) / d out
+    float g = out - y[m];                          // d l2_loss(y − out) / d out
+    float ll = 0.f;                                // log_loss's l_b
+    if (sig) {
+      const float yy = y[m];
+      const float pr = 1.f / (1.f + expf(-out));
+      ll = -yy * logf(pr + kLogLossEps) - (1.f - yy) * logf(1.f - pr + kLogLossEps);
+      g = ((1.f - yy) / (1.f - pr + kLogLossEps) - yy / (pr + kLogLossEps)) * pr * (1.f - pr) /
+          (float)B;
+    }
     if constexpr (DET) {
 #pragma unroll
       for (int j = 0; j < NJ; ++j) part[j] = 0.f;
-      if (l == 0) lossb[m] = 0.5 * ((double)g * (double)g);
+      if (l == 0) lossb[m] = sig ? (double)ll : 0.5 * ((double)g * (double)g);
     } else {
       sb += g;
-      sl += 0.5f * g * g;
+      sl += sig ? ll : 0.5f * g * g;
     }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -1236,10 +1256,10 @@ __global__ __launch_bounds__(256) void dfm_train_head(
       if constexpr (DET) {
         if (c < D) rowv[m * D + c] = part[j];
       } else {
-        if (c < F) atomicAdd(&dw[clamp_id(x[c], M)], g * Wp[c]);
+        if (c < F1) atomicAdd(&dw[clamp_id(x[c], M)], g * Wp[c]);
       }
-      if (c >= F + k && c < D) {
-        const int n = c - F - k;
+      if (c >= FK && c < D) {
+        const int n = c - FK;
         GL[m * ldh + n] = cv[j] > 0.f ? g * Wp[c] : 0.f;   // relu' of the last layer
       }
     }
@@ -1261,27 +1281,40 @@ __global__ __launch_bounds__(256) void dfm_train_head(
 // DET: the same value is stored at its occurrence instead, dE [B·F][k], and the
 // occurrence's dw value g_m·Wp[f] (the head's expression) in wb [B·F], for the
 // segment pass (StoredContrib).
+// `head`: without DEEP there is no dX0 term (dX0 unread); without FM no
+// g·Wp[F+c]·(s − e) term and wb = 0 (Wp then holds h_L's entries only).
 template <bool DET>
 __global__ __launch_bounds__(256) void dfm_train_scatter(
     const int32_t* __restrict__ idx, int64_t B, int F, const float* __restrict__ E, int64_t M,
     int k, const float* __restrict__ dX0, const float* __restrict__ gvec,
-    const float* __restrict__ Wp, float* __restrict__ dE, float* __restrict__ wb) {
+    const float* __restrict__ Wp, float* __restrict__ dE, float* __restrict__ wb, int head) {
   const int l = threadIdx.x & 63;
+  const bool fm = head & HHFM_DFM_HEAD_FM, deep = head & HHFM_DFM_HEAD_DEEP;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
   const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
   for (int64_t m = wave; m < B; m += nwave) {
     const int32_t* x = idx + m * F;
     const float g = gvec[m];
     if constexpr (DET)
-      for (int f = l; f < F; f += kWave) wb[m * F + f] = g * Wp[f];
+      for (int f = l; f < F; f += kWave) wb[m * F + f] = fm ? g * Wp[f] : 0.f;
     for (int c = l; c < k; c += kWave) {
-      float s = 0.f;
-      for (int f = 0; f < F; ++f) s += E[(int64_t)clamp_id(x[f], M) * k + c];
-      const float gy2 = g * Wp[F + c];
+      float s = 0.f, gy2 = 0.f;
+      if (fm) {
+        for (int f = 0; f < F; ++f) s += E[(int64_t)clamp_id(x[f], M) * k + c];
+        gy2 = g * Wp[F + c];
+      }
       for (int f = 0; f < F; ++f) {
         const int64_t id = clamp_id(x[f], M);
-        const float e = E[id * k + c];
-        const float v = dX0[m * (int64_t)(F * k) + f * k + c] + gy2 * (s - e);
+        float v;
+        if (fm) {
+          const float e = E[id * k + c];
+          if (deep)
+            v = dX0[m * (int64_t)(F * k) + f * k + c] + gy2 * (s - e);
+          else
+            v = gy2 * (s - e);
+        } else {
+          v = dX0[m * (int64_t)(F * k) + f * k + c];
+        }
         if constexpr (DET)
           dE[(m * F + f) * k + c] = v;
         else
@@ -1290,6 +1323,10 @@ __global__ __launch_bounds__(256) void dfm_train_scatter(
     }
   }
 }
+
+// log_loss's one division by B, on the summed row losses (default step: after
+// the head's atomics; deterministic: after det_scalars stored the ordered sum)
+__global__ void dfm_mean_loss(float* scal, float Bf) { scal[kScalDataLoss] /= Bf; }
 
 // The DeepFM / AFM workspace allocator and the part of the layout the two
 // plans share.  Offsets are in floats, every region rounded up to 64 floats.
@@ -1323,7 +1360,7 @@ struct TrainWs {
 
 struct DfmTrainPlan : TrainWs {
   int64_t Bp;
-  int L, D0;
+  int L, D0, dL;                     // dL: the last layer's width (0 without layers)
   int d[kDfmTrainMaxLayers + 1];     // d[0] = F·k, d[l+1] = layer l width
   int64_t off_WtP[kDfmTrainMaxLayers], off_WP[kDfmTrainMaxLayers];
   int64_t off_dW[kDfmTrainMaxLayers], off_db[kDfmTrainMaxLayers];
@@ -1332,9 +1369,12 @@ struct DfmTrainPlan : TrainWs {
   int64_t off_dX0, off_g, off_dWp;
 };
 
+// `min_layers` 0: a step without the deep part may come with no layer list
+// (d_L = 0: the dWp region is [F + k], no per-layer scratch).
 static bool dfm_train_plan(int64_t B, int F, int k, int64_t M, int L, const int32_t* dims,
-                           DfmTrainPlan& p) {
-  if (L < 1 || L > kDfmTrainMaxLayers || F < 1 || k < 4 || k % 4) return false;
+                           DfmTrainPlan& p, int min_layers = 1) {
+  if (L < min_layers || L > kDfmTrainMaxLayers || F < 1 || k < 4 || k % 4) return false;
+  if (L > 0 && !dims) return false;
   p = DfmTrainPlan{};
   p.L = L;
   p.D0 = F * k;
@@ -1343,10 +1383,11 @@ static bool dfm_train_plan(int64_t B, int F, int k, int64_t M, int L, const int3
     if (dims[i] < 1) return false;
     p.d[i + 1] = dims[i];
   }
-  if (F + k + p.d[L] > kDfmHeadMaxCols) return false;
+  p.dL = L > 0 ? p.d[L] : 0;
+  if (F + k + p.dL > kDfmHeadMaxCols) return false;
   p.Bp = pad8(B > 0 ? B : 1);
   p.take_state_head(M, k);
-  p.off_dWp = p.take(F + k + p.d[L]);
+  p.off_dWp = p.take(F + k + p.dL);
   p.take_state_tail(M);
   // per-batch scratch (dW / db are written by the step before the optimizer reads them)
   for (int i = 0; i < L; ++i) {
@@ -1709,7 +1750,7 @@ static bool afm_train_plan(int64_t B, int F, int k, int A, int64_t M, AfmTrainPl
 // per wave of every λ-carrying variable's optimizer grid.
 static bool dfm_det_plan(int64_t B, int F, int k, int64_t M, const DfmTrainPlan& p, DetPlan& d) {
   if (B > 0x7fffffff) return false;
-  const int D = F + k + p.d[p.L];
+  const int D = F + k + p.dL;
   int64_t ss = det_sumsq_floats(D);
   for (int i = 0; i < p.L; ++i) ss += det_sumsq_floats((int64_t)p.d[i] * p.d[i + 1]);
   return det_plan_regions(B, F, M, B * F * k, ss, B * F, B * D, d);
@@ -1985,28 +2026,47 @@ extern "C" int hhfm_dfm_train_state_bytes(int32_t F, int32_t k, int64_t features
 }
 
 // The DeepFM step: the default path (det false; scratch unused), or the
-// deterministic one on `scratch` (hhfm_dfm_train_det_scratch bytes).
+// deterministic one on `scratch` (hhfm_dfm_train_det_scratch bytes).  `head`
+// (include/hhfm.h "DeepFM heads"; FM | DEEP is the reference default): without
+// DEEP no layer is read and no transpose or GEMM runs; a variable the head
+// gives no gradient is left out of the optimizer's list.
 static int dfm_train_step_impl(const int32_t* idx, const float* y, int64_t B, int32_t F, float* E,
                                float* w, int64_t features_M, int32_t k, int32_t nlayers,
                                const int32_t* layer_dims, float* const* W, float* const* bias,
                                float* Wp, float* bp, float lr, float lambda_l2,
                                int32_t optimizer, float* const* acc, void* workspace,
                                size_t ws_bytes, bool det, void* scratch, size_t scratch_bytes,
-                               float* loss, void* stream) {
+                               float* loss, void* stream,
+                               int32_t head = HHFM_DFM_HEAD_FM | HHFM_DFM_HEAD_DEEP) {
   DfmTrainPlan p;
   DetPlan d{};
-  if (B < 0 || features_M < 1 || !layer_dims ||
-      !dfm_train_plan(B, F, k, features_M, nlayers, layer_dims, p) ||
+  if (head & ~(HHFM_DFM_HEAD_FM | HHFM_DFM_HEAD_DEEP | HHFM_DFM_HEAD_SIGMOID)) return HHFM_EINVAL;
+  const bool fm = head & HHFM_DFM_HEAD_FM, deep = head & HHFM_DFM_HEAD_DEEP;
+  const bool sig = head & HHFM_DFM_HEAD_SIGMOID;
+  if (!fm && !deep) return HHFM_EINVAL;
+  if (B < 0 || features_M < 1 || (deep && !layer_dims) ||
+      !dfm_train_plan(B, F, k, features_M, nlayers, layer_dims, p, deep ? 1 : 0) ||
       (det && !dfm_det_plan(B, F, k, features_M, p, d)))
     return HHFM_EINVAL;
   if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
-  if (!E || !w || !W || !bias || !Wp || !bp || !loss || !workspace) return HHFM_EINVAL;
+  if (!E || !w || (deep && (!W || !bias)) || !Wp || !bp || !loss || !workspace)
+    return HHFM_EINVAL;
   if (B > 0 && (!idx || !y)) return HHFM_EINVAL;
   const int L = p.L;
-  for (int i = 0; i < L; ++i)
+  for (int i = 0; deep && i < L; ++i)
     if (!W[i] || !bias[i]) return HHFM_EINVAL;
-  // acc: E, w, W_0..W_{L-1}, b_0..b_{L-1}, Wp, bp
-  if (!slots_ok(optimizer, acc, 2 * L + 4)) return HHFM_EINVAL;
+  // acc: E, w, W_0..W_{L-1}, b_0..b_{L-1}, Wp, bp; a head looks only at the
+  // slots of the variables it moves
+  if (fm && deep) {
+    if (!slots_ok(optimizer, acc, 2 * L + 4)) return HHFM_EINVAL;
+  } else if (optimizer != HHFM_OPT_SGD) {
+    if (!acc || !acc[0] || (fm && !acc[1]) || !acc[2 + 2 * L] || !acc[3 + 2 * L])
+      return HHFM_EINVAL;
+    for (int i = 0; deep && i < 2 * L; ++i)
+      if (!acc[2 + i]) return HHFM_EINVAL;
+  }
+  // the head's concat columns: the present parts of [y1 (F) | y2 (k) | h_L (d_L)]
+  const int D = (fm ? F + k : 0) + (deep ? p.dL : 0);
   if (ws_bytes < (size_t)p.total * 4) return HHFM_EWORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (det) {
@@ -2021,7 +2081,31 @@ static int dfm_train_step_impl(const int32_t* idx, const float* y, int64_t B, in
   char* sc = reinterpret_cast<char*>(scratch);
   auto sf = [&](size_t off) { return reinterpret_cast<float*>(sc + off); };
 
-  if (B > 0) {
+  if (B > 0 && !deep) {
+    // the FM head: head, scatter (or the det row pass and segment pass); no GEMM chain
+    hipLaunchKernelGGL(det ? dfm_train_head<true> : dfm_train_head<false>,
+                       dim3(grid_for_n(B * 64 / 8)), dim3(256), 0, st, idx, y, B, F, E, w,
+                       features_M, k, nullptr, 0, (int64_t)0, Wp, bp, nullptr, at(p.off_g),
+                       at(p.off_dWp), at(p.off_dw), scal, det ? sf(d.heads) : nullptr,
+                       det ? reinterpret_cast<double*>(sc + d.loss) : nullptr, head);
+    if (!det) {
+      if (sig) hipLaunchKernelGGL(dfm_mean_loss, dim3(1), dim3(1), 0, st, scal, (float)B);
+      hipLaunchKernelGGL(dfm_train_scatter<false>, dim3(grid_for_n(B * 64)), dim3(256), 0, st,
+                         idx, B, F, E, features_M, k, nullptr, at(p.off_g), Wp, at(p.off_dE),
+                         nullptr, head);
+    } else {
+      hipLaunchKernelGGL(det_columns, dim3(D), dim3(256), 0, st, sf(d.heads), B, (int64_t)D,
+                         at(p.off_dWp));
+      hipLaunchKernelGGL(dfm_train_scatter<true>, dim3(grid_for_n(B * 64)), dim3(256), 0, st, idx,
+                         B, F, E, features_M, k, nullptr, at(p.off_g), Wp, sf(d.rowvec),
+                         sf(d.bias), head);
+      const OccSource src{idx, nullptr, F, 0, 0, 0, 0, 0};
+      const int rc = det_scatter(d, sc, src, F, B, features_M, E, k, at(p.off_dE), at(p.off_dw),
+                                 at(p.off_g), scal, StoredContrib{sf(d.rowvec), sf(d.bias), k}, st);
+      if (rc != 0) return rc;
+      if (sig) hipLaunchKernelGGL(dfm_mean_loss, dim3(1), dim3(1), 0, st, scal, (float)B);
+    }
+  } else if (B > 0) {
     // weights: Wᵀ zero-padded (forward Bt) and W zero-padded (backward Bt)
     for (int i = 0; i < L; ++i) {
       const int din = p.d[i], dout = p.d[i + 1];
@@ -2053,9 +2137,9 @@ static int dfm_train_step_impl(const int32_t* idx, const float* y, int64_t B, in
                        features_M, k, at(p.off_H[L]), p.d[L], ldL, Wp, bp, at(p.off_G[L]),
                        at(p.off_g), at(p.off_dWp), at(p.off_dw), scal,
                        det ? sf(d.heads) : nullptr,
-                       det ? reinterpret_cast<double*>(sc + d.loss) : nullptr);
+                       det ? reinterpret_cast<double*>(sc + d.loss) : nullptr, head);
+    if (sig && !det) hipLaunchKernelGGL(dfm_mean_loss, dim3(1), dim3(1), 0, st, scal, (float)B);
     if (det) {
-      const int D = F + k + p.d[L];
       hipLaunchKernelGGL(det_columns, dim3(D), dim3(256), 0, st, sf(d.heads), B, (int64_t)D,
                          at(p.off_dWp));
     }
@@ -2087,15 +2171,16 @@ static int dfm_train_step_impl(const int32_t* idx, const float* y, int64_t B, in
     if (!det) {
       hipLaunchKernelGGL(dfm_train_scatter<false>, dim3(grid_for_n(B * 64)), dim3(256), 0, st,
                          idx, B, F, E, features_M, k, at(p.off_dX0), at(p.off_g), Wp,
-                         at(p.off_dE), nullptr);
+                         at(p.off_dE), nullptr, head);
     } else {
       hipLaunchKernelGGL(dfm_train_scatter<true>, dim3(grid_for_n(B * 64)), dim3(256), 0, st, idx,
                          B, F, E, features_M, k, at(p.off_dX0), at(p.off_g), Wp, sf(d.rowvec),
-                         sf(d.bias));
+                         sf(d.bias), head);
       const OccSource src{idx, nullptr, F, 0, 0, 0, 0, 0};
       const int rc = det_scatter(d, sc, src, F, B, features_M, E, k, at(p.off_dE), at(p.off_dw),
                                  at(p.off_g), scal, StoredContrib{sf(d.rowvec), sf(d.bias), k}, st);
       if (rc != 0) return rc;
+      if (sig) hipLaunchKernelGGL(dfm_mean_loss, dim3(1), dim3(1), 0, st, scal, (float)B);
     }
   }
   // optimizer: λ only on the layer weights and the concat projection
@@ -2103,8 +2188,9 @@ static int dfm_train_step_impl(const int32_t* idx, const float* y, int64_t B, in
   OptVar vars[2 * kDfmTrainMaxLayers + 4];
   int nv = 0;
   vars[nv++] = {E, at(p.off_dE), slot_of(optimizer, acc, 0), features_M * k, 0.f, k, true, false};
-  vars[nv++] = {w, at(p.off_dw), slot_of(optimizer, acc, 1), features_M, 0.f, 1, true, false};
-  for (int i = 0; i < L; ++i) {
+  if (fm)   // (without FM dw stays zero: the head adds nothing, the segment pass stores 0)
+    vars[nv++] = {w, at(p.off_dw), slot_of(optimizer, acc, 1), features_M, 0.f, 1, true, false};
+  for (int i = 0; deep && i < L; ++i) {
     const int64_t n = (int64_t)p.d[i] * p.d[i + 1];
     if (B == 0) {   // no backward pass wrote this batch's dW / db
       (void)hipMemsetAsync(at(p.off_dW[i]), 0, n * 4, st);
@@ -2115,8 +2201,8 @@ static int dfm_train_step_impl(const int32_t* idx, const float* y, int64_t B, in
     vars[nv++] = {bias[i], at(p.off_db[i]), slot_of(optimizer, acc, 2 + L + i), p.d[i + 1], 0.f,
                   1, false, false};
   }
-  vars[nv++] = {Wp, at(p.off_dWp), slot_of(optimizer, acc, 2 + 2 * L), F + k + p.d[L], lambda_l2,
-                1, false, true};
+  vars[nv++] = {Wp, at(p.off_dWp), slot_of(optimizer, acc, 2 + 2 * L), D, lambda_l2, 1, false,
+                true};
   vars[nv++] = {bp, scal + kScalBiasGrad, slot_of(optimizer, acc, 3 + 2 * L), 1, 0.f, 1, false,
                 false};
   uint8_t* touched = reinterpret_cast<uint8_t*>(at(p.off_touch));
@@ -2147,6 +2233,32 @@ extern "C" int hhfm_dfm_train_step_det(const int32_t* idx, const float* y, int64
   return dfm_train_step_impl(idx, y, B, F, E, w, features_M, k, nlayers, layer_dims, W, bias, Wp,
                              bp, lr, lambda_l2, optimizer, acc, workspace, ws_bytes, true, scratch,
                              scratch_bytes, loss, stream);
+}
+
+extern "C" int hhfm_dfm_train_step_head(const int32_t* idx, const float* y, int64_t B, int32_t F,
+                                        float* E, float* w, int64_t features_M, int32_t k,
+                                        int32_t nlayers, const int32_t* layer_dims,
+                                        float* const* W, float* const* bias, float* Wp,
+                                        float* bp, float lr, float lambda_l2, int32_t optimizer,
+                                        float* const* acc, void* workspace, size_t ws_bytes,
+                                        float* loss, void* stream, int32_t head) {
+  return dfm_train_step_impl(idx, y, B, F, E, w, features_M, k, nlayers, layer_dims, W, bias, Wp,
+                             bp, lr, lambda_l2, optimizer, acc, workspace, ws_bytes, false,
+                             nullptr, 0, loss, stream, head);
+}
+
+extern "C" int hhfm_dfm_train_step_head_det(const int32_t* idx, const float* y, int64_t B,
+                                            int32_t F, float* E, float* w, int64_t features_M,
+                                            int32_t k, int32_t nlayers,
+                                            const int32_t* layer_dims, float* const* W,
+                                            float* const* bias, float* Wp, float* bp, float lr,
+                                            float lambda_l2, int32_t optimizer,
+                                            float* const* acc, void* workspace, size_t ws_bytes,
+                                            void* scratch, size_t scratch_bytes, float* loss,
+                                            void* stream, int32_t head) {
+  return dfm_train_step_impl(idx, y, B, F, E, w, features_M, k, nlayers, layer_dims, W, bias, Wp,
+                             bp, lr, lambda_l2, optimizer, acc, workspace, ws_bytes, true, scratch,
+                             scratch_bytes, loss, stream, head);
 }
 
 extern "C" int hhfm_dfm_train_det_scratch(int64_t B, int32_t F, int32_t k, int64_t features_M,

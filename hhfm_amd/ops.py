@@ -309,27 +309,77 @@ def dfm_prepare_weights(layers, biases, mlp_dtype: torch.dtype, F: int, k: int):
 DFM_PROJ = {False: 0, True: 1, None: 2, "ctx": 3, "item": 4}
 
 
+# DeepFM heads (include/hhfm.h HHFM_DFM_HEAD_*): which parts the concat
+# projection sees, and the sigmoid output of loss_type "logloss"
+DFM_HEAD_FM = 1
+DFM_HEAD_DEEP = 2
+DFM_HEAD_SIGMOID = 4
+
+
+def dfm_head_word(use_fm: bool = True, use_deep: bool = True, loss_type: str = "mse") -> int:
+    """The head word of the reference constructor's use_fm / use_deep /
+    loss_type (DFM.py:131-144); 3 is the reference default."""
+    if not (use_fm or use_deep):
+        raise ValueError("a DeepFM head needs use_fm or use_deep")
+    if loss_type not in ("mse", "logloss"):
+        raise ValueError("loss_type can be either 'logloss' or 'mse'")
+    return ((DFM_HEAD_FM if use_fm else 0) | (DFM_HEAD_DEEP if use_deep else 0)
+            | (DFM_HEAD_SIGMOID if loss_type == "logloss" else 0))
+
+
+def _head_ws_extra(head: int, F: int, k: int, dims) -> int:
+    """HHFM_DFM_HEAD_WS_EXTRA: room after the plan for the deep head's
+    zero-prefixed projection."""
+    if head & DFM_HEAD_FM or not head & DFM_HEAD_DEEP:
+        return 0
+    return ((F + k + int(dims[-1])) * 4 + 255) & ~255
+
+
+def _head_dims(head: int, dims):
+    """The workspace queries' layer list: the model's, or one unit-wide layer
+    for an FM head that carries none (its kernels touch no workspace)."""
+    dims = [int(d) for d in dims]
+    if not dims and not head & DFM_HEAD_DEEP:
+        return [1]
+    return dims
+
+
 def dfm_forward(idx: torch.Tensor, E: torch.Tensor, w: torch.Tensor, Wt, bias, dims,
                 mlp_dtype: torch.dtype, Wp: torch.Tensor, bp: float,
                 out: Optional[torch.Tensor] = None,
-                proj=None, plan: int = 0) -> torch.Tensor:
+                proj=None, plan: int = 0, head: Optional[int] = None) -> torch.Tensor:
     """DeepFM.out (DFM.py:104-137) for rows ``idx`` [B, F] -> float32 [B].
 
     ``proj``: projected layer 0 (include/hhfm.h, ABI v3) — None lets the
     library decide (include/hhfm.h HHFM_DFM_PROJ_AUTO), True / False force it
     on / off, "ctx" projects the context fields 2..F-1 only and "item" every
     field but the item (bf16 MLP).  ``plan``: PLAN_* flags (fp32 MLP:
-    PLAN_EXACT_FP32, _ROW_FM, _UNSTAGED, _UNGROUPED; bf16 MLP: _NARROW)."""
+    PLAN_EXACT_FP32, _ROW_FM, _UNSTAGED, _UNGROUPED; bf16 MLP: _NARROW).
+    ``head``: a :func:`dfm_head_word` (include/hhfm.h "DeepFM heads") — ``Wp`` is
+    then that head's projection, the layer lists may be empty without
+    DFM_HEAD_DEEP, and DFM_HEAD_SIGMOID returns the sigmoid; None is the
+    reference default on the entry point without a head word."""
     _idx(idx, "idx")
     dev = _need_cuda(idx, E, w, Wp, *Wt, *bias)
     B, F = idx.shape
     M, k = E.shape
-    md = _dtype_code(Wt[0])
-    if mlp_dtype != Wt[0].dtype:
-        raise TypeError("Wt dtype must equal mlp_dtype")
     if out is None:
         out = torch.empty(B, dtype=torch.float32, device=dev)
     nat = native()
+    if head is not None:
+        md = _dtype_code(Wt[0]) if len(Wt) else (1 if mlp_dtype == torch.bfloat16 else 0)
+        nbytes = nat.dfm_forward_workspace_ex(B, F, k, M, _head_dims(head, dims), md,
+                                              DFM_PROJ[proj])
+        ws = _workspace(dev, nbytes + _head_ws_extra(head, F, k, dims))
+        nat.dfm_forward_head(idx.data_ptr(), B, F, E.data_ptr(), M, k, _dtype_code(E),
+                             w.data_ptr(), list(dims), [t.data_ptr() for t in Wt],
+                             [t.data_ptr() for t in bias], md, Wp.data_ptr(), float(bp),
+                             out.data_ptr(), DFM_PROJ[proj], int(plan), ws.data_ptr(),
+                             ws.numel(), _stream(dev), int(head))
+        return out
+    md = _dtype_code(Wt[0])
+    if mlp_dtype != Wt[0].dtype:
+        raise TypeError("Wt dtype must equal mlp_dtype")
     nbytes = nat.dfm_forward_workspace_ex(B, F, k, M, list(dims), md, DFM_PROJ[proj])
     ws = _workspace(dev, nbytes)
     nat.dfm_forward(idx.data_ptr(), B, F, E.data_ptr(), M, k, _dtype_code(E), w.data_ptr(),
@@ -342,15 +392,34 @@ def dfm_forward(idx: torch.Tensor, E: torch.Tensor, w: torch.Tensor, Wt, bias, d
 def dfm_catalog_topk(qidx: torch.Tensor, E: torch.Tensor, w: torch.Tensor, Wt, bias, dims,
                      Wp: torch.Tensor, bp: float, item_col: int, item_row_begin: int,
                      item_count: int, K: int, global_item_base: int = 0,
-                     chunk_rows: int = 1 << 20, proj=None, plan: int = 0):
-    """DeepFM.topk (DFM.py:219-231) -> (scores [B,K], ids [B,K]); ``proj`` and
-    ``plan`` as in :func:`dfm_forward` (rows = B x item_count)."""
+                     chunk_rows: int = 1 << 20, proj=None, plan: int = 0,
+                     head: Optional[int] = None):
+    """DeepFM.topk (DFM.py:219-231) -> (scores [B,K], ids [B,K]); ``proj``,
+    ``plan`` and ``head`` as in :func:`dfm_forward` (rows = B x item_count).
+    With a head the scores are the pre-sigmoid z whatever DFM_HEAD_SIGMOID says
+    (the sigmoid is monotone: the same id lists)."""
     _idx(qidx, "qidx")
     dev = _need_cuda(qidx, E, w, Wp, *Wt, *bias)
     B, F = qidx.shape
     M, k = E.shape
-    md = _dtype_code(Wt[0])
     nat = native()
+    if head is not None:
+        md = _dtype_code(Wt[0]) if len(Wt) else 0
+        nbytes = nat.dfm_catalog_topk_workspace_ex(B, F, k, M, item_count,
+                                                   _head_dims(head, dims), md, chunk_rows,
+                                                   DFM_PROJ[proj])
+        ws = _workspace(dev, nbytes + _head_ws_extra(head, F, k, dims))
+        top_s = torch.empty(B, K, dtype=torch.float32, device=dev)
+        top_i = torch.empty(B, K, dtype=torch.int32, device=dev)
+        nat.dfm_catalog_topk_head(qidx.data_ptr(), B, F, item_col, E.data_ptr(), M, k,
+                                  _dtype_code(E), w.data_ptr(), list(dims),
+                                  [t.data_ptr() for t in Wt], [t.data_ptr() for t in bias], md,
+                                  Wp.data_ptr(), float(bp), item_row_begin, item_count,
+                                  global_item_base, K, chunk_rows, top_s.data_ptr(),
+                                  top_i.data_ptr(), DFM_PROJ[proj], int(plan), ws.data_ptr(),
+                                  ws.numel(), _stream(dev), int(head))
+        return top_s, top_i
+    md = _dtype_code(Wt[0])
     nbytes = nat.dfm_catalog_topk_workspace_ex(B, F, k, M, item_count, list(dims), md,
                                                chunk_rows, DFM_PROJ[proj])
     ws = _workspace(dev, nbytes)

@@ -192,8 +192,10 @@ def hhfm_partial_fit(model, data) -> float:
 
 def dfm_partial_fit(model, data) -> float:
     """DeepFM.partial_fit (DFM.py:214-217): one TF Adagrad step on every
-    variable (DFM.py:155), loss l2_loss(y − out) + l2_reg on the concat
-    projection and the layer weights (DFM.py:143-152)."""
+    variable the model's head gives a gradient (DFM.py:155; without use_deep
+    no layer moves, without use_fm not feature_bias), loss l2_loss(y − out) or
+    log_loss(y, sigmoid(out)) + l2_reg on the concat projection and, with
+    use_deep, the layer weights (DFM.py:139-152)."""
     W = model.weights
     L = len(model.deep_layers)
     names = (["feature_embeddings", "feature_bias"] + [f"layer_{i}" for i in range(L)]
@@ -214,12 +216,17 @@ def dfm_partial_fit(model, data) -> float:
             float(model.l2_reg), _ADAGRAD, [st[n].data_ptr() for n in names], ws.data_ptr(),
             ws.numel())
     tail = (st["loss"].data_ptr(), ops._stream(model.device))
-    if getattr(model, "deterministic", False):
+    head = getattr(model, "head", 3)
+    head = () if head == 3 else (head,)   # the default model: the entry points without a head
+    det = getattr(model, "deterministic", False)
+    if det:
         sc = _det_scratch(model, st, B,
                           size_fn=lambda b: nat.dfm_train_det_scratch(b, F, k, M, dims))
-        nat.dfm_train_step_det(*args, sc.data_ptr(), sc.numel(), *tail)
+        step = nat.dfm_train_step_head_det if head else nat.dfm_train_step_det
+        step(*args, sc.data_ptr(), sc.numel(), *tail, *head)
     else:
-        nat.dfm_train_step(*args, *tail)
+        step = nat.dfm_train_step_head if head else nat.dfm_train_step
+        step(*args, *tail, *head)
     model._prep = None   # the scoring path's prepared (transposed / bf16) weights are stale
     return float(st["loss"].item())
 

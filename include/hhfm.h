@@ -705,6 +705,96 @@ int hhfm_dfm_train_step_det(const int32_t* idx, const float* y, int64_t B, int32
                             float* const* acc, void* workspace, size_t ws_bytes, void* scratch,
                             size_t scratch_bytes, float* loss, void* stream);
 
+/* ------------------------------------------------------------------------
+ * DeepFM heads — the reference constructor's use_fm / use_deep / loss_type
+ * (DFM.py:131-152, 199-204) as a run-time word of four entry points, whose
+ * argument lists are those of hhfm_dfm_forward_ex, hhfm_dfm_catalog_topk_ex,
+ * hhfm_dfm_train_step and hhfm_dfm_train_step_det plus `head`:
+ *   head = HHFM_DFM_HEAD_FM | HHFM_DFM_HEAD_DEEP | HHFM_DFM_HEAD_SIGMOID
+ * Neither FM nor DEEP set, or any other bit, is HHFM_EINVAL.  FM | DEEP (3)
+ * is the model of the entry points above and runs their code: the same bits.
+ *
+ * Layouts.  Wp is the reference's concat_projection of that head — [F + k]
+ * (FM), [d_L] (DEEP), [F + k + d_L] (both): the present parts in the order
+ * y1, y2, h_L.  Without DEEP nlayers may be 0 and layer_dims / Wt / W / bias
+ * NULL: nothing reads them.  w is a valid [features_M] array for every head.
+ *
+ * Forward.  z = [present parts]·Wp + bp; out = z, or 1/(1 + expf(−z)) with
+ * SIGMOID (one elementwise pass over out after the forward).
+ *   FM head: the FM part's own row kernels (the ones the fp32 split forward
+ *     takes its `base` from; any k % 4 == 0, fp32 or bf16 table); proj_mode,
+ *     plan and mlp_dtype are accepted and unused, the workspace is not touched
+ *     and may be NULL.
+ *   DEEP head: the full forward on a copy of Wp with F + k exact zeros in
+ *     front, built on the stream in the workspace: ws_bytes must cover the
+ *     *_workspace_ex size of the call plus HHFM_DFM_HEAD_WS_EXTRA(F, k, d_L)
+ *     (the copy lies after the plan; the other heads need no extra).  Adding exact
+ *     zeros changes no bit of h_L·Wp + bp — given finite w and table values:
+ *     an Inf or NaN there would reach the score through 0·Inf.
+ * Bad ids are read as row 0, as everywhere (flag them with hhfm_check_ids).
+ *
+ * Catalog top-K ranks by z and returns z, for every head: the sigmoid is
+ * monotone, so the id lists are the reference's, and merges of item shards
+ * stay exact because they merge z.  One difference: where two items' fp32
+ * sigmoid values are equal although their z differ, the reference's top_k
+ * orders them by index and this code by z.
+ *
+ * Loss and step.  Without SIGMOID  Σ_b (y_b − z_b)²/2, as hhfm_dfm_train_step.
+ * With SIGMOID TF-1.x tf.losses.log_loss at its defaults:
+ *   loss = (Σ_b l_b)/B,  l_b = −y·logf(p + ε) − (1 − y)·logf(1 − p + ε),
+ *   ε = 1e-7f, p = 1/(1 + expf(−z)), one division by B, 0 at B = 0, y any
+ *   real (the reference's epoch loop feeds −1; the formula stays finite);
+ *   g_b = ∂loss/∂z_b = ((1 − y)/(1 − p + ε) − y/(p + ε))·p·(1 − p)/B.
+ * Everything downstream of g_b is hhfm_dfm_train_step's expressions (dWp, dbp,
+ * dw, the last layer's delta, the table scatter) over the present parts; the
+ * l2 term is λ·‖Wp‖²/2, plus Σ_l λ·‖W_l‖²/2 only with DEEP (DFM.py:146-152).
+ * A variable without a gradient does not move (TF's minimize skips it), nor
+ * does its slot: without DEEP no W_l / b_l, without FM not w — the table then
+ * receives the deep gradient only.  acc keeps the 2L+4 order; the entries of
+ * variables that do not move are ignored (they may be NULL).  Without DEEP
+ * the step launches no transpose and no GEMM.
+ * hhfm_dfm_train_workspace / _state_bytes / _det_scratch serve every head
+ * (upper bounds; the dWp region keeps its full-concat size and a head uses its
+ * first entries), so heads of one layer list can share a workspace.  The
+ * deterministic step keeps its promise for every head (the row loss l_b is
+ * formed in float and summed in double in the scalar order, then divided by
+ * B once).
+ * ---------------------------------------------------------------------- */
+#define HHFM_DFM_HEAD_FM 1
+#define HHFM_DFM_HEAD_DEEP 2
+#define HHFM_DFM_HEAD_SIGMOID 4
+#define HHFM_DFM_HEAD_WS_EXTRA(F, k, dL) \
+  ((((size_t)(F) + (size_t)(k) + (size_t)(dL)) * 4 + 255) & ~(size_t)255)
+int hhfm_dfm_forward_head(const int32_t* idx, int64_t B, int32_t F, const void* E,
+                          int64_t features_M, int32_t k, int32_t dtype, const float* w,
+                          int32_t nlayers, const int32_t* layer_dims, const void* const* Wt,
+                          const float* const* bias, int32_t mlp_dtype, const float* Wp,
+                          float bp, float* out, int32_t proj_mode, int32_t plan,
+                          void* workspace, size_t ws_bytes, void* stream, int32_t head);
+int hhfm_dfm_catalog_topk_head(const int32_t* qidx, int64_t B, int32_t F, int32_t item_col,
+                               const void* E, int64_t features_M, int32_t k, int32_t dtype,
+                               const float* w, int32_t nlayers, const int32_t* layer_dims,
+                               const void* const* Wt, const float* const* bias,
+                               int32_t mlp_dtype, const float* Wp, float bp,
+                               int32_t item_row_begin, int32_t item_count,
+                               int32_t global_item_base, int32_t K, int64_t chunk_rows,
+                               float* top_score, int32_t* top_idx, int32_t proj_mode,
+                               int32_t plan, void* workspace, size_t ws_bytes, void* stream,
+                               int32_t head);
+int hhfm_dfm_train_step_head(const int32_t* idx, const float* y, int64_t B, int32_t F, float* E,
+                             float* w, int64_t features_M, int32_t k, int32_t nlayers,
+                             const int32_t* layer_dims, float* const* W, float* const* bias,
+                             float* Wp, float* bp, float lr, float lambda_l2,
+                             int32_t optimizer, float* const* acc, void* workspace,
+                             size_t ws_bytes, float* loss, void* stream, int32_t head);
+int hhfm_dfm_train_step_head_det(const int32_t* idx, const float* y, int64_t B, int32_t F,
+                                 float* E, float* w, int64_t features_M, int32_t k,
+                                 int32_t nlayers, const int32_t* layer_dims, float* const* W,
+                                 float* const* bias, float* Wp, float* bp, float lr,
+                                 float lambda_l2, int32_t optimizer, float* const* acc,
+                                 void* workspace, size_t ws_bytes, void* scratch,
+                                 size_t scratch_bytes, float* loss, void* stream, int32_t head);
+
 /* tf.nn.top_k(scores, K) over a materialised score matrix [B][ld] (first N
  * columns), K <= 64; ids reported as global_item_base + column. */
 int hhfm_topk_dense(const float* scores, int64_t B, int32_t N, int64_t ld, int32_t K,

@@ -11,8 +11,11 @@ the default DeepFM step (150/200/150), and --det, on a build that has them,
 also the deterministic AFM (keep 1 and [0.8, 0.5]) and DeepFM steps; --pooling
 adds the default HHFM step (NG = 10) and, on a build that has
 hhfm_train_step_pool, the (max, max, max) and (mean, mean, mean) pooled steps
-alternated with it (two rounds).
-usage: python scripts/train_step_time.py LIBDIR TAG [--drop] [--det] [--dfm] [--pooling]"""
+alternated with it (two rounds); --heads adds the default DeepFM step and
+forward (fp32 MLP, 5000 and 2^20 rows) and, on a build that has the DeepFM
+heads, the FM-head / deep-head / logloss steps, and at 2^22 rows the FM-head
+forward with and without the sigmoid pass beside hhfm_fm_score_rows.
+usage: python scripts/train_step_time.py LIBDIR TAG [--drop] [--det] [--dfm] [--pooling] [--heads]"""
 import importlib.machinery
 import importlib.util
 import json
@@ -226,5 +229,71 @@ if det or "--dfm" in sys.argv:
         res["afm_keep0.8_0.5_us"] = timed(afm_step((0.8, 0.5), None))
         res["afm_det_keep0.8_0.5_us"] = timed(afm_step((0.8, 0.5), asc))
         res["dfm_det_us"] = timed(dfm_step(dsc))
+if "--heads" in sys.argv:
+    layers = [150, 200, 150]
+    dims = [F * k] + layers
+    D = F + k + layers[-1]
+    shapes = ([(M, k), (M,)] + [(i, o_) for i, o_ in zip(dims, dims[1:])] + [(o_,) for o_ in layers]
+              + [(D,), (1,)])
+    hpar, hacc = params(shapes, [0.01, 0.3] + [0.08] * 3 + [0.08] * 3 + [0.1, 0.01])
+    hp, ha = [t.data_ptr() for t in hpar], [t.data_ptr() for t in hacc]
+    hws = torch.zeros(nat.dfm_train_workspace(B, F, k, M, layers), dtype=torch.uint8, device="cuda")
+    # the forward's layout: layer weights transposed [N][K], K padded to 8
+    Wt, kin = [], F * k
+    for n_ in layers:
+        Wt.append(dev(rng.normal(0, 0.08, (n_, kin)).astype(np.float32)))
+        kin = (n_ + 7) & ~7
+
+    def step_head(head):
+        """The default step (head None: the entry point without a head word) or a head's."""
+        def fn():
+            args = (X.data_ptr(), y.data_ptr(), B, F, hp[0], hp[1], M, k, layers, hp[2:5], hp[5:8],
+                    hp[8], hp[9], 0.01, 0.01, 0, ha, hws.data_ptr(), hws.numel(), loss.data_ptr(), st)
+            if head is None:
+                nat.dfm_train_step(*args)
+            else:
+                nat.dfm_train_step_head(*args, head)
+        return fn
+
+    def forward(rows, head, Xr, out, fws):
+        def fn():
+            args = (Xr.data_ptr(), rows, F, hp[0], M, k, 0, hp[1], layers,
+                    [t.data_ptr() for t in Wt], hp[5:8], 0, hp[8], 0.01, out.data_ptr(), 2, 0,
+                    fws.data_ptr(), fws.numel(), st)
+            if head is None:
+                nat.dfm_forward(*args)
+            else:
+                nat.dfm_forward_head(*args, head)
+        return fn
+
+    def rows_of(n):
+        Xr = X[torch.randint(0, B, (n,), device="cuda", generator=torch.Generator("cuda")
+                             .manual_seed(n))].contiguous()
+        fws = torch.empty(nat.dfm_forward_workspace_ex(n, F, k, M, layers, 0, 2) + 4096,
+                          dtype=torch.uint8, device="cuda")
+        return Xr, torch.empty(n, device="cuda"), fws
+
+    has = hasattr(nat, "dfm_train_step_head")
+    for rnd in (1, 2):
+        res[f"dfm_step_us_round{rnd}"] = timed(step_head(None))
+        if has:
+            res[f"dfm_step_head3_us_round{rnd}"] = timed(step_head(3))
+    for n in (B, 1 << 20):
+        Xr, out, fws = rows_of(n)
+        reps = dict(reps=7, n=40) if n == B else dict(reps=5, n=5)
+        for rnd in (1, 2):
+            res[f"dfm_fwd_{n}_us_round{rnd}"] = timed(forward(n, None, Xr, out, fws), **reps)
+            if has:
+                res[f"dfm_fwd_head3_{n}_us_round{rnd}"] = timed(forward(n, 3, Xr, out, fws), **reps)
+    if has:
+        for name, head in (("fm", 1), ("deep", 2), ("fm_logloss", 5), ("both_logloss", 7)):
+            res[f"dfm_step_{name}_us"] = timed(step_head(head))
+        n = 1 << 22
+        Xr, out, fws = rows_of(n)
+        res["fm_head_fwd_4M_us"] = timed(forward(n, 1, Xr, out, fws), reps=5, n=5)
+        res["fm_head_sigmoid_fwd_4M_us"] = timed(forward(n, 5, Xr, out, fws), reps=5, n=5)
+        res["fm_score_rows_4M_us"] = timed(
+            lambda: nat.fm_score_rows_ex(Xr.data_ptr(), n, F, hp[0], M, k, 0, hp[1], 0.01,
+                                         out.data_ptr(), 0, 0, st), reps=5, n=5)
 res = {k_: ([round(v, 2) for v in vs] if isinstance(vs, list) else vs) for k_, vs in res.items()}
 print(json.dumps(res))

@@ -1,8 +1,19 @@
 """FM — drop-in for Newcode/FM.py (model class, Train harness, FM_main).
 
 Scoring runs on the gfx950 kernels:
-  * ``score_rows`` / ``sess.run(model.out)`` -> hhfm_fm_score_rows (FM.py:99-120)
-  * ``topk(A, tp)`` -> hhfm_catalog_topk, HHFM_MODE_FM (FM.py:172-198)
+  * ``score_rows`` / ``sess.run(model.out)`` -> hhfm_fm_score_rows (FM.py:99-120);
+    with ``batch_norm=1`` hhfm_fm_score_rows_scaled on the moving statistics
+  * ``topk(A, tp)`` -> hhfm_catalog_topk, HHFM_MODE_FM (FM.py:172-198); the
+    reference's catalog score does not pass through the batch-norm layer
+    (FM.py:181 is commented out)
+
+``batch_norm=1`` (FM.py:111-112, :160-166; include/hhfm.h "FM batch norm") adds
+the weights ``bn_gamma``, ``bn_beta``, ``bn_moving_mean``, ``bn_moving_variance``.
+Two things the reference's graph does are deliberately not reproduced: it
+builds both branches outside ``tf.cond``, so every ``sess.run(out)`` would also
+move the moving averages with the fed batch — here scoring never writes a
+weight; and batch statistics exist only inside ``partial_fit`` —
+``train_phase: True`` through ``sess.run(model.out, …)`` raises.
 """
 from __future__ import annotations
 
@@ -16,6 +27,10 @@ from . import harness, ops
 from ._model import Fetch, Placeholder, ScoringModel
 
 method = "FM"
+
+# tf.contrib.layers.batch_norm(decay=0.9) and its default epsilon; the update
+# factor is float(1.0 - decay), the complement formed in double as TF forms it
+BN_DECAY, BN_EPS = 0.9, 0.001
 
 
 def parse_args(dataname, factor, TopK, argv=None):
@@ -61,9 +76,11 @@ class FM(ScoringModel):
         self.batch_norm = batch_norm
         self.verbose = verbose
         self.train_rmse, self.valid_rmse, self.test_rmse = [], [], []
-        if batch_norm:
-            raise NotImplementedError("batch_norm=1 is not part of the scoring path "
-                                      "(the reference runs with batch_norm=0, FM.py:50)")
+        self.bn_eps = BN_EPS
+        self.bn_update = float(1.0 - BN_DECAY)
+        if batch_norm and self.deterministic:
+            raise NotImplementedError("deterministic=True has no batch_norm=1 step "
+                                      "(hhfm_fm_train_step_bn adds its batch sums with atomics)")
         self._setup_device(device, table_dtype)
         self._init_graph()
 
@@ -78,20 +95,33 @@ class FM(ScoringModel):
 
     def _initialize_weights(self):
         """FM.py:150-158: E ~ N(0, 0.01), feature_bias = 0, bias = 0."""
-        return {
+        W = {
             "feature_embeddings": self._normal((self.features_M, self.hidden_factor), 0.01,
                                                self.random_seed),
             "feature_bias": torch.zeros(self.features_M, 1, device=self.device),
             "bias": torch.zeros((), device=self.device),
         }
+        if self.batch_norm:   # contrib batch_norm's variables (beta, gamma, moving_*)
+            k = self.hidden_factor
+            W["bn_beta"] = torch.zeros(k, device=self.device)
+            W["bn_gamma"] = torch.ones(k, device=self.device)
+            W["bn_moving_mean"] = torch.zeros(k, device=self.device)
+            W["bn_moving_variance"] = torch.ones(k, device=self.device)
+        return W
 
     # -- scoring ------------------------------------------------------------------
     def score_rows(self, X) -> np.ndarray:
         """FM.out for full rows [user, item, ctx...] -> float32 [B, 1]."""
         idx = self._idx(X)
-        w = self.weights["feature_bias"].reshape(-1)
-        out = ops.fm_score_rows(idx, self.table, w, float(self.weights["bias"]))
-        return self._np_out(out)
+        W = self.weights
+        w = W["feature_bias"].reshape(-1)
+        if not self.batch_norm:
+            return self._np_out(ops.fm_score_rows(idx, self.table, w, float(W["bias"])))
+        # the layer on the moving statistics: a = γ/√(mv + eps) weights the
+        # columns, Σ(β − mm·a) joins the bias
+        a = (W["bn_gamma"] / torch.sqrt(W["bn_moving_variance"] + self.bn_eps)).contiguous()
+        w0 = W["bias"] + (W["bn_beta"] - W["bn_moving_mean"] * a).sum()
+        return self._np_out(ops.fm_score_rows(idx, self.table, w, float(w0), scale=a))
 
     def catalog_topk(self, q, begin, count, K):
         """Top-K of items [begin, begin+count) by (u+f)·(i+f) + w_i (FM.py:172-185)
@@ -108,6 +138,9 @@ class FM(ScoringModel):
 
     def _run_fetch(self, fetch, feed):
         if fetch is self.out:
+            if self.batch_norm and bool(np.any(feed.get(self.train_phase, False))):
+                raise NotImplementedError("batch_norm=1: batch statistics exist only inside "
+                                          "partial_fit; feed train_phase False to score")
             return self.score_rows(feed[self.train_features])
         return super()._run_fetch(fetch, feed)
 

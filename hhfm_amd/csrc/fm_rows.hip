@@ -78,11 +78,14 @@ HHFM_DEV void load_ids(int32_t (&id)[U][F], const int32_t* __restrict__ idx,
 // default policy lets them evict the re-read `w` lines and context rows from
 // the Infinity Cache: 4.21 -> 4.11 ms at configs[1] (ids and output
 // non-temporal as well: 4.53 ms; profiles/r04_k1_nt_ab.txt)
-template <int F, int LPR, bool BF16, bool HAS_W, int NTM>
+// SCALED (hhfm_fm_score_rows_scaled): column c enters the row sum as
+// scale[c]·½(s² − q); a lane loads the scale of its C::kElems columns once,
+// before the row loop.  Everything else is the same code.
+template <int F, int LPR, bool BF16, bool HAS_W, int NTM, bool SCALED = false>
 __global__ __launch_bounds__(256) void fm_rows_fast(
     const int32_t* __restrict__ idx, int64_t B, const char* __restrict__ E,
     int64_t M, const float* __restrict__ w, float w0, float* __restrict__ out,
-    int32_t* __restrict__ status) {
+    int32_t* __restrict__ status, const float* __restrict__ scale) {
   constexpr int U = RowsPerLane<F>::value;
   constexpr int RPW = kWave / LPR;  // rows per wave per unroll slot
   constexpr int RPI = RPW * U;      // rows per wave-iteration
@@ -97,6 +100,12 @@ __global__ __launch_bounds__(256) void fm_rows_fast(
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
   const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
   const int64_t stride = nwave * RPI;
+
+  [[maybe_unused]] float sc[C::kElems];
+  if constexpr (SCALED) {
+#pragma unroll
+    for (int e = 0; e < C::kElems; ++e) sc[e] = scale[sub * C::kElems + e];
+  }
 
   int64_t base = wave * RPI;
   int32_t raw[U][F];
@@ -159,7 +168,8 @@ __global__ __launch_bounds__(256) void fm_rows_fast(
           s += c[u][f].v[e];
           q += c[u][f].v[e] * c[u][f].v[e];
         }
-        t += 0.5f * (s * s - q);
+        if constexpr (SCALED) t += sc[e] * (0.5f * (s * s - q));
+        else t += 0.5f * (s * s - q);
       }
       t = group_sum_dpp<LPR>(t);
       float fb = 0.f;
@@ -492,11 +502,11 @@ __global__ __launch_bounds__(256) void fm_rows_fast_hot(
 }
 
 // Generic fallback (any k, any F <= 64): one wave per row, lanes stride over k.
-template <bool BF16>
+template <bool BF16, bool SCALED = false>
 __global__ __launch_bounds__(256) void fm_rows_generic(
     const int32_t* __restrict__ idx, int64_t B, int F, const char* __restrict__ E,
     int64_t M, int k, const float* __restrict__ w, float w0,
-    float* __restrict__ out, int32_t* __restrict__ status) {
+    float* __restrict__ out, int32_t* __restrict__ status, const float* __restrict__ scale) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
   const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
@@ -515,7 +525,8 @@ __global__ __launch_bounds__(256) void fm_rows_generic(
         s += v;
         q += v * v;
       }
-      t += 0.5f * (s * s - q);
+      if constexpr (SCALED) t += scale[e] * (0.5f * (s * s - q));
+      else t += 0.5f * (s * s - q);
     }
     t = group_sum<kWave>(t);
     float fb = 0.f;
@@ -845,16 +856,36 @@ static void launch_fm_fast(const int32_t* idx, int64_t B, const char* E,
   const bool big = M * (int64_t)LPR * 16 >= ((int64_t)1 << 30);
   if (w && nt)
     hipLaunchKernelGGL((fm_rows_fast<F, LPR, BF16, true, 1>), dim3(grid),
-                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status);
+                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status, nullptr);
   else if (w && big && F >= 2)
     hipLaunchKernelGGL((fm_rows_fast<F, LPR, BF16, true, 2>), dim3(grid),
-                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status);
+                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status, nullptr);
   else if (w)
     hipLaunchKernelGGL((fm_rows_fast<F, LPR, BF16, true, 0>), dim3(grid),
-                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status);
+                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status, nullptr);
   else
     hipLaunchKernelGGL((fm_rows_fast<F, LPR, BF16, false, 0>), dim3(grid),
-                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status);
+                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status, nullptr);
+}
+
+// fm_rows_fast<SCALED>: the plain launcher's grid and its rule for tables of
+// 1 GiB and more (NTM 2); no flags, never the LDS-tail kernel
+template <int F, int LPR, bool BF16>
+static void launch_fm_scaled(const int32_t* idx, int64_t B, const char* E,
+                             int64_t M, const float* w, float w0, const float* scale,
+                             float* out, int32_t* status, hipStream_t s) {
+  constexpr int RPB = 4 * (kWave / LPR) * RowsPerLane<F>::value;
+  const int grid = grid_for(B, RPB, s);
+  const bool big = M * (int64_t)LPR * 16 >= ((int64_t)1 << 30);
+  if (w && big && F >= 2)
+    hipLaunchKernelGGL((fm_rows_fast<F, LPR, BF16, true, 2, true>), dim3(grid),
+                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status, scale);
+  else if (w)
+    hipLaunchKernelGGL((fm_rows_fast<F, LPR, BF16, true, 0, true>), dim3(grid),
+                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status, scale);
+  else
+    hipLaunchKernelGGL((fm_rows_fast<F, LPR, BF16, false, 0, true>), dim3(grid),
+                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status, scale);
 }
 
 template <int F, int LPR, bool BF16>
@@ -909,6 +940,17 @@ static bool try_fm_fast(const int32_t* idx, int64_t B, int F, const char* E,
     HHFM_F_SWITCH(launch_fm_fast, true, idx, B, E, M, w, w0, out, nt, status, s)
   } else {
     HHFM_F_SWITCH(launch_fm_fast, false, idx, B, E, M, w, w0, out, nt, status, s)
+  }
+  return true;
+}
+
+static bool try_fm_scaled(const int32_t* idx, int64_t B, int F, const char* E,
+                          int64_t M, int lpr, bool bf16, const float* w, float w0,
+                          const float* scale, float* out, int32_t* status, hipStream_t s) {
+  if (bf16) {
+    HHFM_F_SWITCH(launch_fm_scaled, true, idx, B, E, M, w, w0, scale, out, status, s)
+  } else {
+    HHFM_F_SWITCH(launch_fm_scaled, false, idx, B, E, M, w, w0, scale, out, status, s)
   }
   return true;
 }
@@ -1003,11 +1045,41 @@ extern "C" int hhfm_fm_score_rows_ex(const int32_t* idx, int64_t B, int32_t F,
     if (bf16)
       hipLaunchKernelGGL(fm_rows_generic<true>, dim3(grid), dim3(256), 0, s, idx,
                          B, F, reinterpret_cast<const char*>(E), features_M, k,
-                         w, w0, out, status);
+                         w, w0, out, status, nullptr);
     else
       hipLaunchKernelGGL(fm_rows_generic<false>, dim3(grid), dim3(256), 0, s,
                          idx, B, F, reinterpret_cast<const char*>(E),
-                         features_M, k, w, w0, out, status);
+                         features_M, k, w, w0, out, status, nullptr);
+  }
+  return (int)hipGetLastError();
+}
+
+extern "C" int hhfm_fm_score_rows_scaled(const int32_t* idx, int64_t B, int32_t F,
+                                         const void* E, int64_t features_M, int32_t k,
+                                         int32_t dtype, const float* w, float w0,
+                                         const float* scale, float* out, int32_t* status,
+                                         void* stream) {
+  if (B < 0 || F < 1 || F > 64 || k < 1 || features_M < 1) return HHFM_EINVAL;
+  if (dtype != HHFM_F32 && dtype != HHFM_BF16) return HHFM_EINVAL;
+  if (!scale) return HHFM_EINVAL;
+  if (B == 0) return HHFM_OK;
+  if (!idx || !E || !out) return HHFM_EINVAL;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool bf16 = dtype == HHFM_BF16;
+  const int lpr = lpr_for(k, dtype);
+  const bool aligned = (reinterpret_cast<uintptr_t>(E) & 15) == 0;
+  if (!(lpr && aligned &&
+        try_fm_scaled(idx, B, F, reinterpret_cast<const char*>(E), features_M, lpr, bf16, w,
+                      w0, scale, out, status, s))) {
+    const int grid = grid_for(B, 4, s);
+    if (bf16)
+      hipLaunchKernelGGL((fm_rows_generic<true, true>), dim3(grid), dim3(256), 0, s, idx, B, F,
+                         reinterpret_cast<const char*>(E), features_M, k, w, w0, out, status,
+                         scale);
+    else
+      hipLaunchKernelGGL((fm_rows_generic<false, true>), dim3(grid), dim3(256), 0, s, idx, B, F,
+                         reinterpret_cast<const char*>(E), features_M, k, w, w0, out, status,
+                         scale);
   }
   return (int)hipGetLastError();
 }

@@ -82,6 +82,20 @@ PYBIND11_MODULE(_hhfm, m) {
           check(rc, "hhfm_fm_score_rows_ex");
         });
 
+  m.def("fm_score_rows_scaled",
+        [](uptr idx, int64_t B, int F, uptr E, int64_t M, int k, int dtype,
+           uptr w, float w0, uptr scale, uptr out, uptr status, uptr stream) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_fm_score_rows_scaled(P<const int32_t>(idx), B, F, P<const void>(E),
+                                           M, k, dtype, P<const float>(w), w0,
+                                           P<const float>(scale), P<float>(out),
+                                           P<int32_t>(status), P<void>(stream));
+          }
+          check(rc, "hhfm_fm_score_rows_scaled");
+        });
+
   m.def("hybrid_score_rows",
         [](uptr idx, int64_t B, int ncols, int ucol, int icol, int c0, int c1,
            int t0, int t1, uptr E, int64_t M, int k, int dtype, uptr out,
@@ -452,6 +466,34 @@ PYBIND11_MODULE(_hhfm, m) {
                                        P<void>(stream));
           }
           check(rc, "hhfm_fm_train_step_ex");
+        });
+
+  m.def("fm_train_bn_workspace", [](int64_t B, int64_t M, int k) {
+    size_t n = 0;
+    check(hhfm_fm_train_bn_workspace(B, M, k, &n), "hhfm_fm_train_bn_workspace");
+    return n;
+  });
+
+  m.def("fm_train_bn_state_bytes",
+        [](int64_t M, int k) { return hhfm_fm_train_bn_state_bytes(M, k); });
+
+  m.def("fm_train_step_bn",
+        [](uptr idx, uptr y, int64_t B, int F, uptr E, uptr w, uptr w0, int64_t M, int k,
+           float lr, float lam, int opt, float keep, uint64_t seed, uptr accE, uptr accw,
+           uptr accw0, uptr ws, size_t ws_bytes, uptr gamma, uptr beta, uptr mm, uptr mv,
+           float eps, float bn_update, uptr acc_gamma, uptr acc_beta, uptr loss, uptr stream) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_fm_train_step_bn(P<const int32_t>(idx), P<const float>(y), B, F,
+                                       P<float>(E), P<float>(w), P<float>(w0), M, k, lr, lam,
+                                       opt, keep, seed, P<float>(accE), P<float>(accw),
+                                       P<float>(accw0), P<void>(ws), ws_bytes, P<float>(gamma),
+                                       P<float>(beta), P<float>(mm), P<float>(mv), eps,
+                                       bn_update, P<float>(acc_gamma), P<float>(acc_beta),
+                                       P<float>(loss), P<void>(stream));
+          }
+          check(rc, "hhfm_fm_train_step_bn");
         });
 
   m.def("dropout_mask", [](uint64_t seed, int site, int64_t rows, int n, float keep, uptr binary,

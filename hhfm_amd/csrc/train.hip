@@ -11,6 +11,9 @@
 //   hhfm_fm_train_step_ex / hhfm_afm_train_step_ex  the same with `--keep` < 1
 //                         (tf.nn.dropout, FM.py:114, AFM.py:126 / :134) on the
 //                         mask of dropout.h; hhfm_dropout_mask writes that mask
+//   hhfm_fm_train_step_bn  the FM step with `--batch_norm 1` (FM.py:111-112,
+//                         :160-166): batch statistics between the k-vector and
+//                         its row sum ("FM with batch_norm=1" below)
 //   hhfm_*_train_step_det the four steps without float atomics, every sum in a
 //                         fixed order ("Deterministic ... steps" below; AFM's and
 //                         DeepFM's reuse their default kernels under a DET flag)
@@ -1785,6 +1788,266 @@ static GemmArgs gemm_plain(int64_t M, int N, int64_t K, const void* A, int64_t l
   return g;
 }
 
+// ---------------------------------------------------------------------------
+// FM with batch_norm=1 (hhfm_fm_train_step_bn; include/hhfm.h "FM batch norm").
+// The layer sits between the k-vector x_bc = ½(s² − q) and its row sum, and its
+// statistics are sums over the whole batch, so the step is a chain of kernels
+// with column sums between them.  Two mappings:
+//   row kernels     one wave per row, lane = column (c = l + 64·j), as
+//                   fm_train_rows: fm_bn_out (out_b, g_b, the loss) and
+//                   fm_bn_scatter (dx_bc and the scatter into dE, dw)
+//   column kernels  the same waves, but the column slab j is the outer loop
+//                   and the wave's rows the inner one, so a lane adds its
+//                   column's terms over its rows in a register (fp32), the
+//                   workgroup's four waves are added through LDS (fp32) and
+//                   ONE double atomicAdd per workgroup and column goes to
+//                   memory (bn_block_add): fm_bn_x (x_bc stored [B][k], Σx),
+//                   fm_bn_m2 (Σ(x − μ)², two-pass), fm_bn_colgrad (dβ, dγ)
+// fm_bn_stats finishes μ, v, inv, a, β − μ·a and moves the moving averages;
+// fm_bn_grads rounds the double sums into the fp32 gradient buffers of γ, β
+// and w0 the optimizer tail reads.  The grid of every kernel but the scatter
+// is capped at kBnMaxBlocks workgroups, so a column receives at most that many
+// double adds and a lane's fp32 partial spans B / (4·kBnMaxBlocks) rows.
+// ---------------------------------------------------------------------------
+constexpr int kBnMaxBlocks = 2048;
+constexpr int kBnSums = 4;   // per column, in double: Σx | Σ(x−μ)² | Σdy | Σdy·x̂ ; then Σg [1]
+constexpr int kBnStats = 4;  // per column, fp32: μ | inv | a | β − μ·a
+
+static int bn_grid(int64_t B) {
+  const int64_t g = (B + 3) / 4;
+  return (int)(g > kBnMaxBlocks ? kBnMaxBlocks : (g < 1 ? 1 : g));
+}
+
+// The FM-BN workspace, in bytes.  Persistent prefix (`state`): fm_train_plan's
+// layout, then dγ [k] | dβ [k] floats — zero-filled once, left zeroed by the
+// step (but Adam's β powers).  Per-batch scratch after it, written before it
+// is read: the double sums (zeroed by the step itself), the fp32 statistics,
+// g [B] and x [B][k].
+struct FmBnPlan {
+  FmTrainPlan fm;
+  size_t off_dgamma, off_dbeta, state, off_sums, off_stats, off_g, off_x, bytes;
+};
+
+static bool fm_bn_plan(int64_t B, int64_t M, int k, FmBnPlan& p) {
+  if (B < 0 || M < 1 || k < 1) return false;
+  p.fm = fm_train_plan(M, k);
+  p.off_dgamma = al256(p.fm.bytes);
+  p.off_dbeta = p.off_dgamma + (size_t)k * 4;
+  p.state = al256(p.off_dbeta + (size_t)k * 4);
+  p.off_sums = p.state;
+  p.off_stats = al256(p.off_sums + ((size_t)kBnSums * k + 1) * 8);
+  p.off_g = al256(p.off_stats + (size_t)kBnStats * k * 4);
+  p.off_x = al256(p.off_g + (size_t)B * 4);
+  p.bytes = al256(p.off_x + (size_t)B * k * 4);
+  return true;
+}
+
+// μ_c as every kernel forms it: the double column sum over B, rounded once
+__device__ __forceinline__ float bn_mean(const double* __restrict__ sum, int c, int64_t B) {
+  return (float)(sum[c] / (double)B);
+}
+
+// dst[c] += the four waves' partials of column c (lane l of every wave holds
+// one), added in fp32 in wave order.  Every thread of the workgroup calls it.
+__device__ __forceinline__ void bn_block_add(float (&red)[4][kWave], float acc, int c, int k,
+                                             double* __restrict__ dst) {
+  const int l = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  red[wv][l] = acc;
+  __syncthreads();
+  if (wv == 0 && c < k)
+    atomicAdd(dst + c, (double)(((red[0][l] + red[1][l]) + red[2][l]) + red[3][l]));
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void fm_bn_x(const int32_t* __restrict__ idx, int64_t B, int F,
+                                               const float* __restrict__ E, int64_t M, int k,
+                                               float* __restrict__ xs, double* __restrict__ sum) {
+  __shared__ float red[4][kWave];
+  const int l = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  for (int c0 = 0; c0 < k; c0 += kWave) {
+    const int c = c0 + l;
+    float acc = 0.f;
+    if (c < k)
+      for (int64_t b = wave; b < B; b += nwave) {
+        const int32_t* x = idx + b * F;
+        float s = 0.f, q = 0.f;
+        for (int f = 0; f < F; ++f) {
+          const float v = E[(int64_t)clamp_id(x[f], M) * k + c];
+          s += v;
+          q += v * v;
+        }
+        const float xv = 0.5f * (s * s - q);
+        xs[b * k + c] = xv;
+        acc += xv;
+      }
+    bn_block_add(red, acc, c, k, sum);
+  }
+}
+
+__global__ __launch_bounds__(256) void fm_bn_m2(int64_t B, int k, const float* __restrict__ xs,
+                                                const double* __restrict__ sum,
+                                                double* __restrict__ m2) {
+  __shared__ float red[4][kWave];
+  const int l = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  for (int c0 = 0; c0 < k; c0 += kWave) {
+    const int c = c0 + l;
+    float acc = 0.f;
+    if (c < k) {
+      const float mu = bn_mean(sum, c, B);
+      for (int64_t b = wave; b < B; b += nwave) {
+        const float d = xs[b * k + c] - mu;
+        acc += d * d;
+      }
+    }
+    bn_block_add(red, acc, c, k, m2);
+  }
+}
+
+// v = Σ(x−μ)²/B (biased), inv = 1/√(v + eps) with IEEE sqrt and division,
+// a = inv·γ, shift = β − μ·a (tf.nn.batch_normalization); then
+// assign_moving_average (zero_debias=False): mm −= (mm − μ)·u, mv −= (mv − v)·u
+__global__ __launch_bounds__(256) void fm_bn_stats(int64_t B, int k,
+                                                   const double* __restrict__ sums,
+                                                   const float* __restrict__ gamma,
+                                                   const float* __restrict__ beta,
+                                                   float* __restrict__ mm, float* __restrict__ mv,
+                                                   float eps, float bn_update,
+                                                   float* __restrict__ stats) {
+  for (int c = threadIdx.x; c < k; c += blockDim.x) {
+    const float mu = bn_mean(sums, c, B);
+    const float v = (float)(sums[k + c] / (double)B);
+    const float inv = __fdiv_rn(1.f, __fsqrt_rn(v + eps));
+    const float a = inv * gamma[c];
+    stats[c] = mu;
+    stats[k + c] = inv;
+    stats[2 * k + c] = a;
+    stats[3 * k + c] = beta[c] - mu * a;
+    mm[c] -= (mm[c] - mu) * bn_update;
+    mv[c] -= (mv[c] - v) * bn_update;
+  }
+}
+
+// out_b = Σ_c y_bc (/ keep · bin_bc) + Σ_f w + w0, y = x·a + (β − μ·a); g_b
+// stored; a wave adds its rows' r²/2 and g in double / fp32 registers and
+// sends one double atomic each when it is done.
+template <bool DROP>
+__global__ __launch_bounds__(256) void fm_bn_out(
+    const int32_t* __restrict__ idx, const float* __restrict__ y, int64_t B, int F,
+    const float* __restrict__ w, const float* __restrict__ w0, int64_t M, int k,
+    const float* __restrict__ xs, const float* __restrict__ stats, float* __restrict__ gb,
+    float* __restrict__ scal, double* __restrict__ gsum, DropoutArgs dr) {
+  const int l = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const float* a = stats + 2 * (int64_t)k;
+  const float* shift = stats + 3 * (int64_t)k;
+  double loss = 0.0, gs = 0.0;
+  for (int64_t b = wave; b < B; b += nwave) {
+    const int32_t* x = idx + b * F;
+    float t = 0.f;
+    [[maybe_unused]] LaneDropout ld;
+    for (int c = l; c < k; c += kWave) {
+      const float yv = xs[b * k + c] * a[c] + shift[c];
+      if constexpr (DROP)
+        t += yv / dr.keep0 * ld.binary(dr, dr.keep0, kDropSiteFm, b, c);
+      else
+        t += yv;
+    }
+    t = group_sum<kWave>(t);
+    float fb = 0.f;
+    for (int f = 0; f < F; ++f) fb += w[clamp_id(x[f], M)];
+    const float out = (t + fb) + w0[0];
+    const float r = y[b] - out;
+    if (l == 0) gb[b] = -r;
+    loss += 0.5 * ((double)r * (double)r);
+    gs += (double)(-r);
+  }
+  if (l == 0 && wave < B) {
+    atomicAdd(scal_loss64(scal), loss);
+    atomicAdd(gsum, gs);
+  }
+}
+
+// dβ_c = Σ_b dy_bc, dγ_c = Σ_b dy_bc·x̂_bc; dy = g·bin/keep, x̂ = (x − μ)·inv.
+// The slab-outer loop does not walk a row's columns in order, so the mask is
+// dropout_element's (a block per element), not LaneDropout's.
+template <bool DROP>
+__global__ __launch_bounds__(256) void fm_bn_colgrad(
+    int64_t B, int k, const float* __restrict__ xs, const float* __restrict__ gb,
+    const float* __restrict__ stats, double* __restrict__ dbeta, double* __restrict__ dgamma,
+    DropoutArgs dr) {
+  __shared__ float red[4][kWave];
+  const int l = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  for (int c0 = 0; c0 < k; c0 += kWave) {
+    const int c = c0 + l;
+    float sb = 0.f, sg = 0.f;
+    if (c < k) {
+      const float mu = stats[c], inv = stats[k + c];
+      for (int64_t b = wave; b < B; b += nwave) {
+        float dy = gb[b];
+        if constexpr (DROP)
+          dy = dy * dropout_element(dr.key0, dr.key1, kDropSiteFm, b, c, dr.keep0) / dr.keep0;
+        sb += dy;
+        sg += dy * ((xs[b * k + c] - mu) * inv);
+      }
+    }
+    bn_block_add(red, sb, c, k, dbeta);
+    bn_block_add(red, sg, c, k, dgamma);
+  }
+}
+
+// the double sums rounded once into the optimizer's fp32 gradient buffers
+__global__ __launch_bounds__(256) void fm_bn_grads(int k, const double* __restrict__ sums,
+                                                   float* __restrict__ dgamma,
+                                                   float* __restrict__ dbeta,
+                                                   float* __restrict__ scal) {
+  for (int c = threadIdx.x; c < k; c += blockDim.x) {
+    dbeta[c] = (float)sums[2 * (int64_t)k + c];
+    dgamma[c] = (float)sums[3 * (int64_t)k + c];
+  }
+  if (threadIdx.x == 0) scal[kScalBiasGrad] = (float)sums[(int64_t)kBnSums * k];
+}
+
+// dx_bc = (a_c / B)·(B·dy_bc − dβ_c − x̂_bc·dγ_c), scattered as fm_train_rows
+// scatters g: dE[x_f][c] += dx_bc·(s_bc − e_fc), dw[x_f] += g_b.  A dropped
+// column still carries the −dβ − x̂·dγ part, so no column is skipped.
+template <bool DROP>
+__global__ __launch_bounds__(256) void fm_bn_scatter(
+    const int32_t* __restrict__ idx, int64_t B, int F, const float* __restrict__ E, int64_t M,
+    int k, const float* __restrict__ xs, const float* __restrict__ gb,
+    const float* __restrict__ stats, const float* __restrict__ dgamma,
+    const float* __restrict__ dbeta, float* __restrict__ dE, float* __restrict__ dw,
+    DropoutArgs dr) {
+  const int l = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const float Bf = (float)B;
+  for (int64_t b = wave; b < B; b += nwave) {
+    const int32_t* x = idx + b * F;
+    const float g = gb[b];
+    [[maybe_unused]] LaneDropout ld;
+    for (int c = l; c < k; c += kWave) {
+      float dy = g;
+      if constexpr (DROP) dy = g * ld.binary(dr, dr.keep0, kDropSiteFm, b, c) / dr.keep0;
+      const float xh = (xs[b * k + c] - stats[c]) * stats[k + c];
+      const float dx = (stats[2 * (int64_t)k + c] / Bf) * (Bf * dy - dbeta[c] - xh * dgamma[c]);
+      float s = 0.f;
+      for (int f = 0; f < F; ++f) s += E[(int64_t)clamp_id(x[f], M) * k + c];
+      for (int f = 0; f < F; ++f) {
+        const int64_t id = clamp_id(x[f], M);
+        atomicAdd(dE + id * k + c, dx * (s - E[id * k + c]));
+      }
+    }
+    for (int f = l; f < F; f += kWave) atomicAdd(dw + clamp_id(x[f], M), g);
+  }
+}
+
 // binary[r][e] = the train kernels' dropout decision (dropout.h) as 0.f / 1.f
 __global__ __launch_bounds__(256) void dropout_mask(DropoutArgs dr, int site, int64_t rows, int n,
                                                     float* __restrict__ binary) {
@@ -1899,6 +2162,87 @@ extern "C" int hhfm_fm_train_step_det(const int32_t* idx, const float* y, int64_
   return fm_train_step_impl(idx, y, B, F, E, w, w0, features_M, k, lr, lam, optimizer, keep, seed,
                             accE, accw, accw0, workspace, ws_bytes, true, scratch, scratch_bytes,
                             loss, stream);
+}
+
+extern "C" int hhfm_fm_train_bn_workspace(int64_t B, int64_t features_M, int32_t k,
+                                          size_t* ws_bytes) {
+  FmBnPlan p;
+  if (!ws_bytes || !fm_bn_plan(B, features_M, k, p)) return HHFM_EINVAL;
+  *ws_bytes = p.bytes;
+  return HHFM_OK;
+}
+
+// the FM-BN workspace's persistent prefix (0: invalid sizes)
+extern "C" size_t hhfm_fm_train_bn_state_bytes(int64_t features_M, int32_t k) {
+  FmBnPlan p;
+  return fm_bn_plan(0, features_M, k, p) ? p.state : 0;
+}
+
+extern "C" int hhfm_fm_train_step_bn(const int32_t* idx, const float* y, int64_t B, int32_t F,
+                                     float* E, float* w, float* w0, int64_t features_M,
+                                     int32_t k, float lr, float lam, int32_t optimizer,
+                                     float keep, uint64_t seed, float* accE, float* accw,
+                                     float* accw0, void* workspace, size_t ws_bytes,
+                                     float* gamma, float* beta, float* moving_mean,
+                                     float* moving_var, float eps, float bn_update,
+                                     float* acc_gamma, float* acc_beta, float* loss,
+                                     void* stream) {
+  // the plain step's checks, in its order ...
+  if (B < 0 || F < 1 || k < 1 || features_M < 1 || !keep_ok(keep)) return HHFM_EINVAL;
+  if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
+  if (!E || !w || !w0 || !loss || !workspace) return HHFM_EINVAL;
+  if (B > 0 && (!idx || !y)) return HHFM_EINVAL;
+  float* const acc[] = {accE, accw, accw0, acc_gamma, acc_beta};
+  if (!slots_ok(optimizer, acc, 3)) return HHFM_EINVAL;
+  FmBnPlan p;
+  if (!fm_bn_plan(B, features_M, k, p)) return HHFM_EINVAL;
+  if (ws_bytes < p.bytes) return HHFM_EWORKSPACE;
+  // ... then the layer's: the moments of an empty batch are NaN in TF
+  if (B == 0 || !(eps > 0.f) || !(bn_update >= 0.f && bn_update <= 1.f)) return HHFM_EINVAL;
+  if (!gamma || !beta || !moving_mean || !moving_var) return HHFM_EINVAL;
+  if (!slots_ok(optimizer, acc + 3, 2)) return HHFM_EINVAL;
+  if (reinterpret_cast<uintptr_t>(workspace) & 7) return HHFM_EINVAL;   // the double sums
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  char* base = reinterpret_cast<char*>(workspace);
+  float* ws = reinterpret_cast<float*>(workspace);
+  float* scal = ws + p.fm.off_scal;
+  float* dgamma = reinterpret_cast<float*>(base + p.off_dgamma);
+  float* dbeta = reinterpret_cast<float*>(base + p.off_dbeta);
+  double* sums = reinterpret_cast<double*>(base + p.off_sums);
+  float* stats = reinterpret_cast<float*>(base + p.off_stats);
+  float* gb = reinterpret_cast<float*>(base + p.off_g);
+  float* xs = reinterpret_cast<float*>(base + p.off_x);
+  const DropoutArgs dr = dropout_args(keep, 1.f, seed);
+  const bool drop = keep < 1.f;
+  const dim3 grid(bn_grid(B)), blk(256);
+  auto k_out = drop ? fm_bn_out<true> : fm_bn_out<false>;
+  auto k_col = drop ? fm_bn_colgrad<true> : fm_bn_colgrad<false>;
+  auto k_scat = drop ? fm_bn_scatter<true> : fm_bn_scatter<false>;
+  if (hipMemsetAsync(sums, 0, ((size_t)kBnSums * k + 1) * 8, st) != hipSuccess)
+    return (int)hipGetLastError();
+  hipLaunchKernelGGL(fm_bn_x, grid, blk, 0, st, idx, B, F, E, features_M, k, xs, sums);
+  hipLaunchKernelGGL(fm_bn_m2, grid, blk, 0, st, B, k, xs, sums, sums + k);
+  hipLaunchKernelGGL(fm_bn_stats, dim3(1), blk, 0, st, B, k, sums, gamma, beta, moving_mean,
+                     moving_var, eps, bn_update, stats);
+  hipLaunchKernelGGL(k_out, grid, blk, 0, st, idx, y, B, F, w,
+                     w0, features_M, k, xs, stats, gb, scal, sums + (int64_t)kBnSums * k, dr);
+  hipLaunchKernelGGL(k_col, grid, blk, 0, st, B, k,
+                     xs, gb, stats, sums + 2 * (int64_t)k, sums + 3 * (int64_t)k, dr);
+  hipLaunchKernelGGL(fm_bn_grads, dim3(1), blk, 0, st, k, sums, dgamma, dbeta, scal);
+  hipLaunchKernelGGL(k_scat, dim3(grid_for_n(B * 64)),
+                     blk, 0, st, idx, B, F, E, features_M, k, xs, gb, stats, dgamma, dbeta,
+                     ws + p.fm.off_dE, ws + p.fm.off_dw, dr);
+  // γ and β are dense variables without an l2 term; the moving statistics are
+  // no optimizer variables (fm_bn_stats has moved them)
+  const OptVar vars[] = {
+      {E, ws + p.fm.off_dE, accE, features_M * k, lam, k, lam == 0.f, true},
+      {w, ws + p.fm.off_dw, accw, features_M, 0.f, 1, true, false},
+      {w0, scal + kScalBiasGrad, accw0, 1, 0.f, 1, false, false},
+      {gamma, dgamma, slot_of(optimizer, acc, 3), k, 0.f, 1, false, false},
+      {beta, dbeta, slot_of(optimizer, acc, 4), k, 0.f, 1, false, false}};
+  uint8_t* touched = reinterpret_cast<uint8_t*>(ws + p.fm.off_touch);
+  return optimizer_tail(vars, (int)std::size(vars), {{idx, B * F}}, features_M, optimizer, lr,
+                        scal, touched, lam, loss, st);
 }
 
 extern "C" int hhfm_train_det_scratch(int64_t B, int32_t occ_per_row, int32_t k,

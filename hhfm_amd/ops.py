@@ -143,19 +143,32 @@ def _status_ptr(status: Optional[torch.Tensor]) -> int:
 
 def fm_score_rows(idx: torch.Tensor, E: torch.Tensor, w: Optional[torch.Tensor],
                   w0: float = 0.0, out: Optional[torch.Tensor] = None,
-                  status: Optional[torch.Tensor] = None, flags: int = 0) -> torch.Tensor:
+                  status: Optional[torch.Tensor] = None, flags: int = 0,
+                  scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """FM.out (FM.py:99-120) for rows ``idx`` [B, F] -> float32 [B].
     ``status``: optional device int32 word the kernel flags bad ids in.
     ``flags``: HHFM_FLAG_* bits of include/hhfm.h, passed through (1 streams
-    the table, 2 / 4 force / refuse the LDS-tail kernel; same bits out)."""
+    the table, 2 / 4 force / refuse the LDS-tail kernel; same bits out).
+    ``scale``: float32 [k] column weights — hhfm_fm_score_rows_scaled, the
+    batch-norm inference score Σ_c scale_c·½(s² − q) + Σw + w0; it takes no flags."""
     _idx(idx, "idx")
-    dev = _need_cuda(idx, E, w, out)
+    dev = _need_cuda(idx, E, w, out, scale)
     B, F = idx.shape
     M, k = E.shape
     if w is not None and (w.dtype != torch.float32 or w.numel() != M):
         raise ValueError("w must be float32 with features_M entries")
     if out is None:
         out = torch.empty(B, dtype=torch.float32, device=dev)
+    if scale is not None:
+        if scale.dtype != torch.float32 or scale.numel() != k or not scale.is_contiguous():
+            raise ValueError("scale must be contiguous float32 with k entries")
+        if flags:
+            raise ValueError("the scaled row score takes no flags")
+        native().fm_score_rows_scaled(idx.data_ptr(), B, F, E.data_ptr(), M, k, _dtype_code(E),
+                                      0 if w is None else w.data_ptr(), float(w0),
+                                      scale.data_ptr(), out.data_ptr(), _status_ptr(status),
+                                      _stream(dev))
+        return out
     native().fm_score_rows_ex(idx.data_ptr(), B, F, E.data_ptr(), M, k, _dtype_code(E),
                               0 if w is None else w.data_ptr(), float(w0),
                               out.data_ptr(), int(flags), _status_ptr(status), _stream(dev))

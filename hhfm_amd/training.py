@@ -133,6 +133,8 @@ def fm_partial_fit(model, data) -> float:
     (of the dropped forward when keep < 1, FM.py:114)."""
     opt = _opt_code(model)
     keep, = _keep(model.keep, 1)
+    if getattr(model, "batch_norm", 0):
+        return _fm_bn_partial_fit(model, data, opt, keep)
     W = model.weights
     st = _state(model, ["feature_embeddings", "feature_bias", "bias"], opt, fixed_ws=True)
     X = model._idx(data["X"])
@@ -150,6 +152,32 @@ def fm_partial_fit(model, data) -> float:
         native().fm_train_step_det(*args, sc.data_ptr(), sc.numel(), *tail)
     else:
         native().fm_train_step_ex(*args, *tail)
+    return float(st["loss"].item())
+
+
+def _fm_bn_partial_fit(model, data, opt, keep) -> float:
+    """FM.partial_fit with batch_norm=1 (FM.py:111-112, :160-166; include/hhfm.h
+    "FM batch norm"): the step's optimizer also acts on bn_gamma / bn_beta, and
+    the forward moves bn_moving_mean / bn_moving_variance."""
+    W = model.weights
+    names = ["feature_embeddings", "feature_bias", "bias", "bn_gamma", "bn_beta"]
+    st = _state(model, names, opt)
+    X = model._idx(data["X"])
+    y = _labels(model, data)
+    B, F = X.shape
+    M, k = W["feature_embeddings"].shape
+    nat = native()
+    ws = _ensure_ws(st, B, model.device, lambda b: nat.fm_train_bn_workspace(b, M, k),
+                    lambda: nat.fm_train_bn_state_bytes(M, k))
+    ptr = lambda n: W[n].data_ptr()  # noqa: E731
+    nat.fm_train_step_bn(
+        X.data_ptr(), y.data_ptr(), B, F, ptr("feature_embeddings"), ptr("feature_bias"),
+        ptr("bias"), M, k, float(model.learning_rate), float(model.lamda_bilinear), opt, keep,
+        _next_seed(model, st), st["feature_embeddings"].data_ptr(),
+        st["feature_bias"].data_ptr(), st["bias"].data_ptr(), ws.data_ptr(), ws.numel(),
+        ptr("bn_gamma"), ptr("bn_beta"), ptr("bn_moving_mean"), ptr("bn_moving_variance"),
+        float(model.bn_eps), float(model.bn_update), st["bn_gamma"].data_ptr(),
+        st["bn_beta"].data_ptr(), st["loss"].data_ptr(), ops._stream(model.device))
     return float(st["loss"].item())
 
 

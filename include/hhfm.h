@@ -140,6 +140,20 @@ int hhfm_fm_score_rows_ex(const int32_t* idx, int64_t B, int32_t F,
                           int32_t dtype, const float* w, float w0, float* out,
                           int32_t flags, int32_t* status, void* stream);
 
+/* Column-weighted form (the inference score of FM with batch_norm=1, "FM
+ * batch norm" below):
+ *   out[b] = (Σ_c scale[c]·½[(Σ_f E[x_bf,c])² − Σ_f E[x_bf,c]²] + Σ_f w[x_bf]) + w0
+ * scale: device float [k], never NULL.  fp32 and bf16 tables, w == NULL, the
+ * status word, bad ids read as row 0 and the generic kernel for rows that are
+ * not whole 16-byte chunks are hhfm_fm_score_rows_ex's.  It takes no flags
+ * and never runs the LDS-tail kernel.  With scale ≡ 1 the output has the bits
+ * of hhfm_fm_score_rows (the same order; a product with 1.0f is exact). */
+int hhfm_fm_score_rows_scaled(const int32_t* idx, int64_t B, int32_t F,
+                              const void* E, int64_t features_M, int32_t k,
+                              int32_t dtype, const float* w, float w0,
+                              const float* scale, float* out, int32_t* status,
+                              void* stream);
+
 /* ------------------------------------------------------------------------
  * H1 — HHFM per-row score (replaces `OUR.PositiveFeadback`,
  * OurModel7.py:105-171 with sum pooling, :14-19)
@@ -528,6 +542,68 @@ int hhfm_fm_train_step_ex(const int32_t* idx, const float* y, int64_t B, int32_t
                           size_t ws_bytes, float* loss, void* stream);
 int hhfm_dropout_mask(uint64_t seed, int32_t site, int64_t rows, int32_t n, float keep,
                       float* binary, void* stream);
+
+/* FM batch norm (`--batch_norm 1` of FM.py:50, :111-112, :160-166).  A
+ * restatement — TensorFlow is not available, TF-level parity is unpinned —
+ * of tf.contrib.layers.batch_norm(x, decay=0.9, center=True, scale=True,
+ * updates_collections=None) on x = FM of shape [B, 1, k], which takes the
+ * non-fused path (rank 3): tf.nn.moments over axes [0, 1],
+ * tf.nn.batch_normalization, assign_moving_average with zero_debias=False.
+ * Variables, all float [k]: gamma (initial 1), beta (0), moving_mean (0),
+ * moving_var (1).  eps is the contrib default 0.001 and bn_update =
+ * float(1.0 − decay), the complement formed in double by the caller as TF
+ * forms it in Python; both are arguments.
+ *
+ * Training forward, per column c over the rows b = 0..B−1:
+ *   x_bc  = ½(s_bc² − q_bc)                   s, q as in hhfm_fm_train_step
+ *   μ_c   = (Σ_b x_bc) / B
+ *   v_c   = (Σ_b (x_bc − μ_c)²) / B           biased, two-pass; never Σx² − Bμ²
+ *   inv_c = 1 / sqrtf(v_c + eps)              IEEE sqrt, one correctly rounded division
+ *   a_c   = inv_c · γ_c
+ *   y_bc  = x_bc · a_c + (β_c − μ_c · a_c)    tf.nn.batch_normalization's form
+ *   FM_OUT_bc = y_bc / keep · bin_bc          dropout site 0, after the layer
+ *   out_b = Σ_c FM_OUT_bc + Σ_f w[x_bf] + w0
+ *   loss  = Σ_b (y_b − out_b)²/2 + λ·Σ E²/2
+ * Backward, g_b = out_b − y_b, dy_bc = g_b · bin_bc / keep, x̂_bc = (x_bc − μ_c)·inv_c:
+ *   dβ_c = Σ_b dy_bc        dγ_c = Σ_b dy_bc · x̂_bc
+ *   dx_bc = (a_c / B) · (B·dy_bc − dβ_c − x̂_bc · dγ_c)
+ *   dE[x_bf][c] += dx_bc · (s_bc − e_bfc)     dw, dw0 as in hhfm_fm_train_step
+ * After the forward, whatever the optimizer:
+ *   mm_c −= (mm_c − μ_c)·bn_update            mv_c −= (mv_c − v_c)·bn_update
+ * The optimizer acts on E (λ; dense when λ > 0, IndexedSlices when λ = 0), w
+ * (sparse), w0, and on γ and β: dense, no l2 term, the usual slots.  The
+ * moving statistics are not optimizer variables.
+ * Every batch sum (Σx, Σ(x−μ)², dβ, dγ, Σg, the loss at every keep) is added in
+ * fp32 inside a workgroup and in double across workgroups, and rounded once.
+ *
+ * Inference (hhfm_fm_score_rows_scaled): the same y with mm, mv in place of
+ * μ, v and no dropout,
+ *   out_b = (Σ_c a_c·x_bc + Σ_f w) + w0',  a_c = γ_c / sqrtf(mv_c + eps),
+ *   w0' = w0 + Σ_c (β_c − mm_c·a_c)
+ * with a and w0' formed by the caller.  Scoring never writes a weight.
+ *
+ * hhfm_fm_train_step_bn is hhfm_fm_train_step_ex with the layer.  Checks: the
+ * plain step's first, in their order; then B = 0 (TF's moments of an empty
+ * batch are NaN), eps not > 0 or NaN, bn_update outside [0, 1], a NULL gamma /
+ * beta / moving_mean / moving_var, a NULL acc_gamma / acc_beta unless SGD, a
+ * workspace that is not 8-byte aligned: HHFM_EINVAL, nothing launched.
+ * Workspace: hhfm_fm_train_bn_workspace(B, ...) bytes, zero-filled once.  Its
+ * first hhfm_fm_train_bn_state_bytes() bytes are the persistent part
+ * (hhfm_train_workspace's layout, then the gradients of γ and β), left zeroed
+ * by the step but for Adam's β powers; the rest is per-batch scratch that
+ * carries no state, so a workspace grown for a larger batch keeps its state
+ * by copying that prefix.  hhfm_fm_train_bn_workspace is HHFM_EINVAL for
+ * B < 0, features_M < 1, k < 1 or a NULL ws_bytes and runs on the host;
+ * hhfm_fm_train_bn_state_bytes is 0 for such sizes. */
+int hhfm_fm_train_bn_workspace(int64_t B, int64_t features_M, int32_t k, size_t* ws_bytes);
+size_t hhfm_fm_train_bn_state_bytes(int64_t features_M, int32_t k);
+int hhfm_fm_train_step_bn(const int32_t* idx, const float* y, int64_t B, int32_t F, float* E,
+                          float* w, float* w0, int64_t features_M, int32_t k, float lr,
+                          float lambda_l2, int32_t optimizer, float keep, uint64_t seed,
+                          float* accE, float* accw, float* accw0, void* workspace,
+                          size_t ws_bytes, float* gamma, float* beta, float* moving_mean,
+                          float* moving_var, float eps, float bn_update, float* acc_gamma,
+                          float* acc_beta, float* loss, void* stream);
 
 /* Deterministic training steps (opt-in; FM and HHFM here, AFM and DeepFM
  * after their default steps below).  The steps above add

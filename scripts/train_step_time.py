@@ -14,8 +14,13 @@ hhfm_train_step_pool, the (max, max, max) and (mean, mean, mean) pooled steps
 alternated with it (two rounds); --heads adds the default DeepFM step and
 forward (fp32 MLP, 5000 and 2^20 rows) and, on a build that has the DeepFM
 heads, the FM-head / deep-head / logloss steps, and at 2^22 rows the FM-head
-forward with and without the sigmoid pass beside hhfm_fm_score_rows.
-usage: python scripts/train_step_time.py LIBDIR TAG [--drop] [--det] [--dfm] [--pooling] [--heads]"""
+forward with and without the sigmoid pass beside hhfm_fm_score_rows; --bn adds
+the plain row score on bench.py's 4.3 GB table at 2^22 and 2^25 rows (the
+automatic plan and HHFM_FLAG_NO_HOT_TAIL) and, on a build that has FM's batch
+norm, hhfm_fm_score_rows_scaled beside them and the batch-norm FM step (keep 1
+and 0.5) alternated with the plain one (two rounds).
+usage: python scripts/train_step_time.py LIBDIR TAG [--drop] [--det] [--dfm] [--pooling]
+       [--heads] [--bn]"""
 import importlib.machinery
 import importlib.util
 import json
@@ -295,5 +300,64 @@ if "--heads" in sys.argv:
         res["fm_score_rows_4M_us"] = timed(
             lambda: nat.fm_score_rows_ex(Xr.data_ptr(), n, F, hp[0], M, k, 0, hp[1], 0.01,
                                          out.data_ptr(), 0, 0, st), reps=5, n=5)
+if "--bn" in sys.argv:
+    # the row score on bench.py's table (8 M users + 8 M items + 12 context ids, k = 64 fp32,
+    # 4.3 GB) at 2^22 and 2^25 rows: the plain entry point (its automatic plan: the LDS-tail
+    # kernel) and with HHFM_FLAG_NO_HOT_TAIL (fm_rows_fast); on a build that has them, the scaled
+    # entry point beside them (two rounds) and the batch-norm FM step beside the plain one
+    has = hasattr(nat, "fm_train_step_bn")
+    nub = nib = 8_000_000
+    Mb = nub + nib + sum(ctx)
+    g = torch.Generator("cuda").manual_seed(1)
+    Eb = torch.empty(Mb, k, device="cuda").normal_(0, 0.01, generator=g)
+    wb = torch.empty(Mb, device="cuda").normal_(0, 0.01, generator=g)
+    nmax = 1 << 25
+    bcols = [torch.randint(0, nub, (nmax,), generator=g, device="cuda", dtype=torch.int32),
+             torch.randint(nub, nub + nib, (nmax,), generator=g, device="cuda", dtype=torch.int32)]
+    o = nub + nib
+    for c in ctx:
+        bcols.append(torch.randint(o, o + c, (nmax,), generator=g, device="cuda",
+                                   dtype=torch.int32))
+        o += c
+    Xb = torch.stack(bcols, 1).contiguous()
+    outb = torch.empty(nmax, device="cuda")
+    scale = torch.empty(k, device="cuda").normal_(1, 0.2, generator=g)
+
+    def rows_plain(n, flags):
+        return lambda: nat.fm_score_rows_ex(Xb.data_ptr(), n, F, Eb.data_ptr(), Mb, k, 0,
+                                            wb.data_ptr(), 0.01, outb.data_ptr(), flags, 0, st)
+
+    def rows_scaled(n):
+        return lambda: nat.fm_score_rows_scaled(Xb.data_ptr(), n, F, Eb.data_ptr(), Mb, k, 0,
+                                                wb.data_ptr(), 0.01, scale.data_ptr(),
+                                                outb.data_ptr(), 0, st)
+
+    for rnd in (1, 2):
+        for n, tagn in ((1 << 22, "4M"), (1 << 25, "32M")):
+            res[f"fm_rows_{tagn}_us_round{rnd}"] = timed(rows_plain(n, 0), reps=5, n=5)
+            res[f"fm_rows_nohot_{tagn}_us_round{rnd}"] = timed(rows_plain(n, 4), reps=5, n=5)
+            if has:
+                res[f"fm_rows_scaled_{tagn}_us_round{rnd}"] = timed(rows_scaled(n), reps=5, n=5)
+    del Eb, wb, Xb, outb
+    if has:
+        bpar, bacc = params([(M, k), (M,), (1,), (k,), (k,)], [0.01, 0.01, 0.01, 0.0, 0.0])
+        bpar[3].fill_(1.0)
+        mm, mv = torch.zeros(k, device="cuda"), torch.ones(k, device="cuda")
+        bws = torch.zeros(nat.fm_train_bn_workspace(B, M, k), dtype=torch.uint8, device="cuda")
+        bp, ba = [t.data_ptr() for t in bpar], [t.data_ptr() for t in bacc]
+
+        def fm_bn(keep):
+            def fn():
+                step[0] += 1
+                nat.fm_train_step_bn(X.data_ptr(), y.data_ptr(), B, F, *bp[:3], M, k, 0.1, 0.1, 0,
+                                     keep, 2016 | step[0] << 32, *ba[:3], bws.data_ptr(),
+                                     bws.numel(), bp[3], bp[4], mm.data_ptr(), mv.data_ptr(), 1e-3,
+                                     float(1.0 - 0.9), ba[3], ba[4], loss.data_ptr(), st)
+            return fn
+
+        for rnd in (1, 2):
+            res[f"fm_keep1_us_round{rnd}"] = timed(fm_plain)
+            res[f"fm_bn_keep1_us_round{rnd}"] = timed(fm_bn(1.0))
+        res["fm_bn_keep0.5_us"] = timed(fm_bn(0.5))
 res = {k_: ([round(v, 2) for v in vs] if isinstance(vs, list) else vs) for k_, vs in res.items()}
 print(json.dumps(res))

@@ -1,15 +1,25 @@
 """HHFM (OurModel7) — drop-in for Newcode/OurModel7.py (OUR, Train, M7_main).
 
-The pairwise-product branches of the reference graph are dead code (their
-Pooling2* results are never used), so with the committed sum pooling
-(OurModel7.py:14-19)
+In the reference's committed text the pairwise-product branches are dead code
+(the three additions that would use their Pooling2* results are commented out,
+OurModel7.py:124 / :141 / :168), so with the committed sum pooling (:14-19)
   h = E[user] + Σ E[ctx] (+ Σ E[time]),   score = h · E[item]   (no bias).
 The three live pools follow the module attributes ``Pooling1C`` (context rows),
 ``Pooling1T`` (time rows) and ``Pooling1F`` (the stack {user, context pool,
 time pool}), read when an ``OUR`` is constructed: "sum", "max" or "mean" (or
 ``ops.POOL_*``), as the reference sets tf.reduce_sum / reduce_max /
 reduce_mean there; ``OUR(..., pooling=(ctx, time, final))`` and ``--pooling``
-override them.  ``Pooling2C`` / ``2T`` / ``2F`` are accepted and ignored.
+override them.
+``OUR(..., two_way=True)`` (``--two_way 1``) puts the three commented-out
+additions back (include/hhfm.h "Two-way pooling"): each pool gains the pool of
+its rows' pair products, the stack the pool of its member products, reduced by
+``Pooling2C`` / ``Pooling2T`` / ``Pooling2F`` (read at construction like
+``Pooling1*``; ``pooling2=(ctx, time, final)`` and ``--pooling2`` override
+them, and ``--pooling2`` implies ``--two_way 1``).  All-sum ``pooling2`` is
+still the two-way model.  It needs at least two context columns and, with time
+fields, two time columns (ValueError otherwise), and has no deterministic step
+(NotImplementedError).  With ``two_way=False`` ``Pooling2*`` are accepted and
+ignored.
 Scoring runs on the gfx950 kernels:
   * ``score_rows`` / ``sess.run(model.PositiveFeadback)`` -> hhfm_hybrid_score_rows
     (OurModel7.py:105-171)
@@ -28,7 +38,8 @@ from ._model import Fetch, Placeholder, ScoringModel, rows_from
 
 method = "M7"
 
-# OurModel7.py:14-19.  Pooling2* feed results the reference's graph never uses.
+# OurModel7.py:14-19.  Pooling2* reduce the pair products, which only the two-way
+# model (OUR(two_way=True)) uses.
 Pooling1C = "sum"
 Pooling2C = "sum"
 Pooling1T = "sum"
@@ -37,14 +48,14 @@ Pooling1F = "sum"
 Pooling2F = "sum"
 
 
-def parse_pooling(text):
-    """``--pooling``: "max" / "mean" / "sum" (all three pools) or
-    "ctx,time,final" -> a (ctx, time, final) triple of mode names."""
+def parse_pooling(text, flag="--pooling"):
+    """``--pooling`` / ``--pooling2``: "max" / "mean" / "sum" (all three pools)
+    or "ctx,time,final" -> a (ctx, time, final) triple of mode names."""
     parts = [t.strip() for t in str(text).split(",")]
     if len(parts) == 1:
         parts = parts * 3
     if len(parts) != 3:
-        raise ValueError(f"--pooling takes one mode or ctx,time,final, got {text!r}")
+        raise ValueError(f"{flag} takes one mode or ctx,time,final, got {text!r}")
     for t in parts:
         ops.pool_mode(t)
     return tuple(parts)
@@ -71,6 +82,12 @@ def parse_args(dataname, factor, Topk, argv=None):
     p.add_argument("--pooling", default=None,
                    help="max | mean | sum, or ctx,time,final (default: the module's "
                         "Pooling1C / Pooling1T / Pooling1F)")
+    p.add_argument("--two_way", type=int, default=0, choices=(0, 1),
+                   help="1: the two-way model (pair products pooled by Pooling2*)")
+    p.add_argument("--pooling2", default=None,
+                   help="max | mean | sum, or ctx,time,final for the pair-product pools "
+                        "(default: the module's Pooling2C / Pooling2T / Pooling2F); "
+                        "implies --two_way 1")
     return p.parse_args(argv)
 
 
@@ -78,8 +95,21 @@ class OUR(ScoringModel):
     def __init__(self, feature_dimension, time_dimension, features_M, n_user, n_item,
                  hidden_factor, learning_rate, lamda_bilinear, optimizer_type, context, time,
                  random_seed=2016, device=None, table_dtype=torch.float32,
-                 deterministic=False, pooling=None):
+                 deterministic=False, pooling=None, two_way=False, pooling2=None):
         self.deterministic = bool(deterministic)
+        self.two_way = bool(two_way)
+        # None: the one-way entry points, exactly as before
+        self.pooling2 = None
+        if self.two_way:
+            if pooling2 is None:
+                pooling2 = (Pooling2C, Pooling2T, Pooling2F)
+            elif isinstance(pooling2, str):
+                pooling2 = parse_pooling(pooling2, "pooling2")
+            ops.pooling_word(pooling2)
+            self.pooling2 = tuple(pooling2)
+            if context and feature_dimension < 2 or time and time_dimension < 2:
+                raise ValueError("two_way=True needs at least two context columns and, with "
+                                 "time fields, at least two time columns")
         if pooling is None:
             pooling = (Pooling1C, Pooling1T, Pooling1F)
         elif isinstance(pooling, str):
@@ -137,7 +167,8 @@ class OUR(ScoringModel):
         """PositiveFeadback for full rows [user, item, ctx..., time...] -> [B,1]."""
         idx = self._idx(X)
         ctx, tim = self._ranges(idx.shape[1])
-        out = ops.hybrid_score_rows(idx, self.table, 0, 1, ctx, tim, pooling=self.pooling)
+        out = ops.hybrid_score_rows(idx, self.table, 0, 1, ctx, tim, pooling=self.pooling,
+                                    pooling2=self.pooling2)
         return self._np_out(out)
 
     def catalog_topk(self, q, begin, count, K):
@@ -145,7 +176,8 @@ class OUR(ScoringModel):
         -> (scores, global item offsets) device tensors [B, K]."""
         ctx, tim = self._ranges(q.shape[1])
         return ops.catalog_topk(q, self.table, ops.MODE_HHFM, int(K), self.n_user + begin,
-                                count, begin, None, 0, ctx, tim, pooling=self.pooling)
+                                count, begin, None, 0, ctx, tim, pooling=self.pooling,
+                                pooling2=self.pooling2)
 
     def topk(self, A, tp):
         _, ids = self.catalog_topk(self._idx(A), 0, self.n_item, tp)
@@ -186,7 +218,9 @@ class Train(harness.Train):
             self.feature_dimension, self.time_dimension, self.features_M, self.n_user,
             self.n_item, args.hidden_factor, args.lr, args.lamda, args.optimizer,
             self.context, self.time, deterministic=bool(getattr(args, "deterministic", 0)),
-            pooling=getattr(args, "pooling", None))
+            pooling=getattr(args, "pooling", None),
+            two_way=bool(getattr(args, "two_way", 0)) or getattr(args, "pooling2", None) is not None,
+            pooling2=getattr(args, "pooling2", None))
 
     def train(self):
         from .training import run_training_hhfm

@@ -155,6 +155,38 @@ __global__ __launch_bounds__(256) void catalog_queries_pool(
   }
 }
 
+// HHFM_MODE_HHFM, two-way (include/hhfm.h "Two-way pooling"): the same walk
+// with h from two_way_h of hhfm_pool.h — the two-way row kernels' h bit for
+// bit; cst stays 0.  A kernel of its own, so that catalog_queries and
+// catalog_queries_pool keep their code and registers.
+template <bool BF16>
+__global__ __launch_bounds__(256) void catalog_queries_two_way(
+    const int32_t* __restrict__ qidx, int64_t B, int64_t Bpad, int ncols,
+    int ucol, int c0, int c1, int t0, int t1, const char* __restrict__ E, int64_t M,
+    int k, PoolModes2 pm, float* __restrict__ H, float* __restrict__ cst) {
+  const int lane = lane_id();
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const int esz = BF16 ? 2 : 4;
+  auto val = [&](int32_t id, int e) -> float {
+    const char* r = E + (int64_t)clamp_id(id, M) * k * esz;
+    return BF16 ? bf16_to_f32(reinterpret_cast<const uint16_t*>(r)[e])
+                : reinterpret_cast<const float*>(r)[e];
+  };
+  for (int64_t b = wave; b < Bpad; b += nwave) {
+    if (b < B) {
+      const int32_t* p = qidx + b * (int64_t)ncols;
+      for (int e = lane; e < k; e += kWave)
+        H[b * k + e] = two_way_h(
+            val(p[ucol], e), [&](int i) { return val(p[c0 + i], e); }, c1 - c0,
+            [&](int i) { return val(p[t0 + i], e); }, t1 - t0, pm).h;
+    } else {
+      for (int e = lane; e < k; e += kWave) H[b * k + e] = 0.f;
+    }
+    if (lane == 0) cst[b] = 0.f;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // 2. main kernel
 // ---------------------------------------------------------------------------
@@ -1446,10 +1478,17 @@ static int catalog_topk_impl(
     int32_t dtype, const float* w, int32_t item_row_begin, int32_t item_count,
     int32_t global_item_base, int32_t K, float* top_score, int32_t* top_idx,
     void* workspace, size_t ws_bytes, int32_t plan, int32_t pooling, int32_t* status,
-    void* stream) {
+    void* stream, bool two_way = false, int32_t pooling2 = 0) {
   PoolModes pm;
+  PoolModes2 pm2{};
   if (!pooling_unpack(pooling, pm)) return HHFM_EINVAL;
   if (pooling != 0 && mode == HHFM_MODE_FM) return HHFM_EINVAL;
+  if (two_way) {
+    if (!pooling2_unpack(pooling, pooling2, pm2) || mode == HHFM_MODE_FM) return HHFM_EINVAL;
+    if (ctx_begin > ctx_end || time_begin > time_end ||
+        !two_way_shape_ok(ctx_end - ctx_begin, time_end - time_begin))
+      return HHFM_EINVAL;
+  }
   if (B < 0 || ncols < 1 || ncols > 64 || k < 1 || features_M < 1) return HHFM_EINVAL;
   if (plan & ~HHFM_PLAN_ALL) return HHFM_EINVAL;
   if (dtype != HHFM_F32 && dtype != HHFM_BF16) return HHFM_EINVAL;
@@ -1490,8 +1529,10 @@ static int catalog_topk_impl(
   // the default up to 8,192 items (one workgroup walks the whole catalog for
   // its 32 queries); HHFM_PLAN_STORE forces the score-matrix path,
   // HHFM_PLAN_FUSED the fused kernel up to the dense limit
+  // (two-way has no form of the fused kernel: it always forms H with
+  // catalog_queries_two_way and runs the main kernels below)
   const bool fused_size = item_count <= 8192 || (plan & HHFM_PLAN_FUSED);
-  if (p.dense && fused_size && K <= 32 && KT <= 8 && p.fS <= kFusedMaxS &&
+  if (!two_way && p.dense && fused_size && K <= 32 && KT <= 8 && p.fS <= kFusedMaxS &&
       (B + kQPerWave - 1) / kQPerWave <= kFusedMaxGroups &&
       ctx_end - ctx_begin <= kFusedMaxCtx && time_end - time_begin <= kFusedMaxCtx &&
       !(plan & (HHFM_PLAN_GEMM | HHFM_PLAN_STORE))) {
@@ -1517,7 +1558,15 @@ static int catalog_topk_impl(
   {
     int64_t blocks = (p.Bpad + 3) / 4;
     if (blocks > 4096) blocks = 4096;
-    if (pooling != 0 && bf16)
+    if (two_way && bf16)
+      hipLaunchKernelGGL(catalog_queries_two_way<true>, dim3((int)blocks), dim3(256), 0, st,
+                         qidx, B, p.Bpad, ncols, user_col, ctx_begin, ctx_end, time_begin,
+                         time_end, Eb, features_M, k, pm2, H, cst);
+    else if (two_way)
+      hipLaunchKernelGGL(catalog_queries_two_way<false>, dim3((int)blocks), dim3(256), 0, st,
+                         qidx, B, p.Bpad, ncols, user_col, ctx_begin, ctx_end, time_begin,
+                         time_end, Eb, features_M, k, pm2, H, cst);
+    else if (pooling != 0 && bf16)
       hipLaunchKernelGGL(catalog_queries_pool<true>, dim3((int)blocks), dim3(256), 0, st,
                          qidx, B, p.Bpad, ncols, user_col, ctx_begin, ctx_end, time_begin,
                          time_end, Eb, features_M, k, pm, H, cst);
@@ -1667,6 +1716,23 @@ extern "C" int hhfm_catalog_topk_pool(
                            time_end, E, features_M, k, dtype, w, item_row_begin, item_count,
                            global_item_base, K, top_score, top_idx, workspace, ws_bytes, plan,
                            pooling, status, stream);
+}
+
+// Two-way: H from catalog_queries_two_way, then the main kernels unchanged;
+// never the small-catalog fused kernel (a two-way form of catalog_fused.h is
+// not built).
+extern "C" int hhfm_catalog_topk_pool2(
+    const int32_t* qidx, int64_t B, int32_t ncols, int32_t mode,
+    int32_t user_col, int32_t ctx_begin, int32_t ctx_end, int32_t time_begin,
+    int32_t time_end, const void* E, int64_t features_M, int32_t k,
+    int32_t dtype, const float* w, int32_t item_row_begin, int32_t item_count,
+    int32_t global_item_base, int32_t K, float* top_score, int32_t* top_idx,
+    void* workspace, size_t ws_bytes, int32_t plan, int32_t pooling, int32_t pooling2,
+    int32_t* status, void* stream) {
+  return catalog_topk_impl(qidx, B, ncols, mode, user_col, ctx_begin, ctx_end, time_begin,
+                           time_end, E, features_M, k, dtype, w, item_row_begin, item_count,
+                           global_item_base, K, top_score, top_idx, workspace, ws_bytes, plan,
+                           pooling, status, stream, true, pooling2);
 }
 
 #if HHFM_FUSED_TIMING

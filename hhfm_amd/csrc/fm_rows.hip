@@ -806,6 +806,186 @@ __global__ __launch_bounds__(256) void hybrid_rows_generic_pool(
 }
 
 // ---------------------------------------------------------------------------
+// Two-way HHFM row kernels (include/hhfm.h "Two-way pooling"; hhfm_pool.h).
+// hybrid_rows_two_way is hybrid_rows_pool's load phase unchanged and a consume
+// phase that forms each pool's pair products from the rows already in
+// registers.  The layout (F, NCTX) is a template parameter — the reference's
+// three layouts are instantiated — so every pair is a compile-time register
+// pair; the six modes stay wave-uniform kernel arguments, branched on around
+// whole straight-line blocks.  The blocks are two_way_mix / two_way_h2 of
+// hhfm_pool.h unrolled: the same steps in the same order, the same bits.
+// ---------------------------------------------------------------------------
+// a[e] = the MODE pool's accumulator over rows c[F0 .. F0 + N)
+template <int F0, int N, int MODE, class C>
+HHFM_DEV void pool1_regs(const C* c, float* a) {
+#pragma unroll
+  for (int e = 0; e < C::kElems; ++e) a[e] = pool_identity(MODE);
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int e = 0; e < C::kElems; ++e) a[e] = pool_step(MODE, a[e], c[F0 + i].v[e]);
+}
+
+// ... over their pair products, (i, j), i < j, i outer
+template <int F0, int N, int MODE, class C>
+HHFM_DEV void pool2_regs(const C* c, float* a) {
+#pragma unroll
+  for (int e = 0; e < C::kElems; ++e) a[e] = pool_identity(MODE);
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = i + 1; j < N; ++j)
+#pragma unroll
+      for (int e = 0; e < C::kElems; ++e)
+        a[e] = pool_step(MODE, a[e], pool_mul(c[F0 + i].v[e], c[F0 + j].v[e]));
+}
+
+// mix[e] = P1 + P2 of the rows c[F0 .. F0 + N)
+template <int F0, int N, class C>
+HHFM_DEV void mix_regs(const C* c, int m1, int m2, float* mix) {
+  float a1[C::kElems], a2[C::kElems];
+  if (m1 == HHFM_POOL_MAX) {
+    pool1_regs<F0, N, HHFM_POOL_MAX>(c, a1);
+  } else {
+    pool1_regs<F0, N, HHFM_POOL_SUM>(c, a1);
+    if (m1 == HHFM_POOL_MEAN) {
+#pragma unroll
+      for (int e = 0; e < C::kElems; ++e) a1[e] = pool_finish(HHFM_POOL_MEAN, a1[e], N);
+    }
+  }
+  if (m2 == HHFM_POOL_MAX) {
+    pool2_regs<F0, N, HHFM_POOL_MAX>(c, a2);
+  } else {
+    pool2_regs<F0, N, HHFM_POOL_SUM>(c, a2);
+    if (m2 == HHFM_POOL_MEAN) {
+#pragma unroll
+      for (int e = 0; e < C::kElems; ++e)
+        a2[e] = pool_finish(HHFM_POOL_MEAN, a2[e], N * (N - 1) / 2);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < C::kElems; ++e) mix[e] = a1[e] + a2[e];
+}
+
+template <int F, int NCTX, int LPR, bool BF16>
+__global__ __launch_bounds__(256) void hybrid_rows_two_way(
+    const int32_t* __restrict__ idx, int64_t B, const char* __restrict__ E, int64_t M,
+    float* __restrict__ out, PoolModes2 pm, int32_t* __restrict__ status) {
+  constexpr int U = RowsPerLane<F>::value;
+  constexpr int RPW = kWave / LPR;
+  constexpr int RPI = RPW * U;
+  constexpr int64_t ROW_BYTES = (int64_t)LPR * 16;
+  constexpr int NT = F - 2 - NCTX;
+  static_assert(NCTX != 1 && NT != 1 && NCTX + NT > 0, "a two-way layout");
+  using C = Chunk<BF16>;
+  const uint32_t M32 = id_limit32(M);
+
+  const int lane = threadIdx.x & (kWave - 1);
+  const int sub = lane & (LPR - 1);
+  const int g = lane / LPR;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const int64_t stride = nwave * RPI;
+
+  int64_t base = wave * RPI;
+  int32_t raw[U][F];
+  bool bad = false;
+  if (base < B) load_ids<F, U>(raw, idx, base, B, g, RPW, F);
+
+  for (; base < B; base += stride) {
+    C c[U][F];
+    int32_t id[U][F];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int f = 0; f < F; ++f) {
+        id[u][f] = clamp_id32(raw[u][f], M32);
+        bad |= id[u][f] != raw[u][f];
+        c[u][f].load(E + (int64_t)id[u][f] * ROW_BYTES + sub * 16);
+      }
+
+    // (unconditional: rows past B read row 0, which keeps vmcnt counting exact)
+    load_ids<F, U>(raw, idx, base + stride, B, g, RPW, F);
+
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      float mc[C::kElems], mt[C::kElems], h1[C::kElems], h2[C::kElems];
+#pragma unroll
+      for (int e = 0; e < C::kElems; ++e) mc[e] = mt[e] = 0.f;
+      if constexpr (NCTX > 0) mix_regs<2, NCTX>(c[u], pm.one.ctx, pm.two.ctx, mc);
+      if constexpr (NT > 0) mix_regs<2 + NCTX, NT>(c[u], pm.one.tim, pm.two.tim, mt);
+      if (pm.one.fin == HHFM_POOL_MAX) {
+#pragma unroll
+        for (int e = 0; e < C::kElems; ++e)
+          h1[e] = pool_h(c[u][0].v[e], mc[e], NCTX, mt[e], NT, HHFM_POOL_MAX);
+      } else if (pm.one.fin == HHFM_POOL_MEAN) {
+#pragma unroll
+        for (int e = 0; e < C::kElems; ++e)
+          h1[e] = pool_h(c[u][0].v[e], mc[e], NCTX, mt[e], NT, HHFM_POOL_MEAN);
+      } else {
+#pragma unroll
+        for (int e = 0; e < C::kElems; ++e)
+          h1[e] = pool_h(c[u][0].v[e], mc[e], NCTX, mt[e], NT, HHFM_POOL_SUM);
+      }
+      if (pm.two.fin == HHFM_POOL_MAX) {
+#pragma unroll
+        for (int e = 0; e < C::kElems; ++e)
+          h2[e] = two_way_h2(c[u][0].v[e], mc[e], NCTX, mt[e], NT, HHFM_POOL_MAX);
+      } else if (pm.two.fin == HHFM_POOL_MEAN) {
+#pragma unroll
+        for (int e = 0; e < C::kElems; ++e)
+          h2[e] = two_way_h2(c[u][0].v[e], mc[e], NCTX, mt[e], NT, HHFM_POOL_MEAN);
+      } else {
+#pragma unroll
+        for (int e = 0; e < C::kElems; ++e)
+          h2[e] = two_way_h2(c[u][0].v[e], mc[e], NCTX, mt[e], NT, HHFM_POOL_SUM);
+      }
+      float t = 0.f;
+#pragma unroll
+      for (int e = 0; e < C::kElems; ++e) t += (h1[e] + h2[e]) * c[u][1].v[e];
+      t = group_sum_dpp<LPR>(t);
+      const int64_t row = base + (int64_t)u * RPW + g;
+      if (sub == 0 && row < B) out[row] = t;
+    }
+  }
+  report_bad_id(status, bad);
+}
+
+// any layout, any k: hybrid_rows_generic_pool with the two-way h
+template <bool BF16>
+__global__ __launch_bounds__(256) void hybrid_rows_generic_two_way(
+    const int32_t* __restrict__ idx, int64_t B, int ncols, int ucol, int icol,
+    int c0, int c1, int t0, int t1, const char* __restrict__ E, int64_t M,
+    int k, float* __restrict__ out, PoolModes2 pm, int32_t* __restrict__ status) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const int esz = BF16 ? 2 : 4;
+  auto val = [&](int32_t id, int e) -> float {
+    const char* r = E + (int64_t)clamp_id(id, M) * k * esz;
+    return BF16 ? bf16_to_f32(reinterpret_cast<const uint16_t*>(r)[e])
+                : reinterpret_cast<const float*>(r)[e];
+  };
+  bool bad = false;
+  for (int64_t row = wave; row < B; row += nwave) {
+    const int32_t* p = idx + row * (int64_t)ncols;
+    for (int c = lane; c < ncols; c += kWave)
+      if (c == ucol || c == icol || (c >= c0 && c < c1) || (c >= t0 && c < t1))
+        bad |= clamp_id(p[c], M) != p[c];
+    float t = 0.f;
+    for (int e = lane; e < k; e += kWave) {
+      const TwoWay w = two_way_h(
+          val(p[ucol], e), [&](int i) { return val(p[c0 + i], e); }, c1 - c0,
+          [&](int i) { return val(p[t0 + i], e); }, t1 - t0, pm);
+      t += w.h * val(p[icol], e);
+    }
+    t = group_sum<kWave>(t);
+    if (lane == 0) out[row] = t;
+  }
+  report_bad_id(status, bad);
+}
+
+// ---------------------------------------------------------------------------
 // dispatch
 // ---------------------------------------------------------------------------
 static int grid_for(int64_t rows, int64_t rows_per_block, hipStream_t s) {
@@ -999,6 +1179,40 @@ static bool try_hybrid_pool(const int32_t* idx, int64_t B, int F, int nctx,
     HHFM_F_SWITCH(launch_hybrid_pool, false, idx, B, nctx, E, M, out, pm, status, s)
   }
   return true;
+}
+
+template <int F, int NCTX, int LPR, bool BF16>
+static void launch_two_way(const int32_t* idx, int64_t B, const char* E, int64_t M, float* out,
+                           PoolModes2 pm, int32_t* status, hipStream_t s) {
+  constexpr int RPB = 4 * (kWave / LPR) * RowsPerLane<F>::value;
+  const int grid = grid_for(B, RPB, s);
+  hipLaunchKernelGGL((hybrid_rows_two_way<F, NCTX, LPR, BF16>), dim3(grid), dim3(256), 0, s,
+                     idx, B, E, M, out, pm, status);
+}
+
+template <int F, int NCTX, bool BF16>
+static bool two_way_lpr(int lpr, const int32_t* idx, int64_t B, const char* E, int64_t M,
+                        float* out, PoolModes2 pm, int32_t* status, hipStream_t s) {
+  switch (lpr) {
+    case 4: launch_two_way<F, NCTX, 4, BF16>(idx, B, E, M, out, pm, status, s); return true;
+    case 8: launch_two_way<F, NCTX, 8, BF16>(idx, B, E, M, out, pm, status, s); return true;
+    case 16: launch_two_way<F, NCTX, 16, BF16>(idx, B, E, M, out, pm, status, s); return true;
+    case 32: launch_two_way<F, NCTX, 32, BF16>(idx, B, E, M, out, pm, status, s); return true;
+    case 64: launch_two_way<F, NCTX, 64, BF16>(idx, B, E, M, out, pm, status, s); return true;
+    default: return false;
+  }
+}
+
+// the fast two-way kernel exists for the reference's layouts: 3 context
+// columns (frappe), 5 + 3 time (jiaju), 5 + 5 (resturant); false: no such kernel
+template <bool BF16>
+static bool try_two_way(const int32_t* idx, int64_t B, int F, int nctx, const char* E,
+                        int64_t M, int lpr, float* out, PoolModes2 pm, int32_t* status,
+                        hipStream_t s) {
+  if (F == 5 && nctx == 3) return two_way_lpr<5, 3, BF16>(lpr, idx, B, E, M, out, pm, status, s);
+  if (F == 10 && nctx == 5) return two_way_lpr<10, 5, BF16>(lpr, idx, B, E, M, out, pm, status, s);
+  if (F == 12 && nctx == 5) return two_way_lpr<12, 5, BF16>(lpr, idx, B, E, M, out, pm, status, s);
+  return false;
 }
 
 static int lpr_for(int64_t k, int dtype) {
@@ -1207,6 +1421,62 @@ extern "C" int hhfm_hybrid_score_rows_pool(const int32_t* idx, int64_t B,
                          idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
                          time_begin, time_end, reinterpret_cast<const char*>(E),
                          features_M, k, out, pm, status);
+  }
+  return (int)hipGetLastError();
+}
+
+// H1, two-way: hybrid_rows_two_way on the reference's canonical layouts,
+// hybrid_rows_generic_two_way everywhere else.  pooling2 == 0 is still the
+// two-way model (no routing to the one-way kernels).
+extern "C" int hhfm_hybrid_score_rows_pool2(const int32_t* idx, int64_t B,
+                                            int32_t ncols, int32_t user_col,
+                                            int32_t item_col, int32_t ctx_begin,
+                                            int32_t ctx_end, int32_t time_begin,
+                                            int32_t time_end, const void* E,
+                                            int64_t features_M, int32_t k,
+                                            int32_t dtype, float* out, int32_t pooling,
+                                            int32_t pooling2, int32_t* status,
+                                            void* stream) {
+  PoolModes2 pm;
+  if (!pooling2_unpack(pooling, pooling2, pm)) return HHFM_EINVAL;
+  if (B < 0 || ncols < 2 || ncols > 64 || k < 1 || features_M < 1)
+    return HHFM_EINVAL;
+  if (dtype != HHFM_F32 && dtype != HHFM_BF16) return HHFM_EINVAL;
+  auto in_range = [&](int c) { return c >= 0 && c < ncols; };
+  if (!in_range(user_col) || !in_range(item_col)) return HHFM_EINVAL;
+  if (ctx_begin > ctx_end || time_begin > time_end) return HHFM_EINVAL;
+  if (ctx_end > ctx_begin && (!in_range(ctx_begin) || ctx_end > ncols))
+    return HHFM_EINVAL;
+  if (time_end > time_begin && (!in_range(time_begin) || time_end > ncols))
+    return HHFM_EINVAL;
+  const int nctx = ctx_end - ctx_begin;
+  const int ntime = time_end - time_begin;
+  if (!two_way_shape_ok(nctx, ntime)) return HHFM_EINVAL;
+  if (B == 0) return HHFM_OK;
+  if (!idx || !E || !out) return HHFM_EINVAL;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool bf16 = dtype == HHFM_BF16;
+  const int lpr = lpr_for(k, dtype);
+  const bool aligned = (reinterpret_cast<uintptr_t>(E) & 15) == 0;
+  const bool canonical = user_col == 0 && item_col == 1 &&
+                         (nctx == 0 || ctx_begin == 2) &&
+                         (ntime == 0 || time_begin == 2 + nctx) &&
+                         2 + nctx + ntime == ncols;
+  const char* Eb = reinterpret_cast<const char*>(E);
+  bool fast = false;
+  if (canonical && lpr && aligned)
+    fast = bf16 ? try_two_way<true>(idx, B, ncols, nctx, Eb, features_M, lpr, out, pm, status, s)
+                : try_two_way<false>(idx, B, ncols, nctx, Eb, features_M, lpr, out, pm, status, s);
+  if (!fast) {
+    const int grid = grid_for(B, 4, s);
+    if (bf16)
+      hipLaunchKernelGGL(hybrid_rows_generic_two_way<true>, dim3(grid), dim3(256), 0, s,
+                         idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
+                         time_begin, time_end, Eb, features_M, k, out, pm, status);
+    else
+      hipLaunchKernelGGL(hybrid_rows_generic_two_way<false>, dim3(grid), dim3(256), 0, s,
+                         idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
+                         time_begin, time_end, Eb, features_M, k, out, pm, status);
   }
   return (int)hipGetLastError();
 }

@@ -145,6 +145,56 @@ PYBIND11_MODULE(_hhfm, m) {
           check(rc, "hhfm_catalog_topk_pool");
         });
 
+  // the two-way entry points (include/hhfm.h "Two-way pooling")
+  m.def("hybrid_score_rows_pool2",
+        [](uptr idx, int64_t B, int ncols, int ucol, int icol, int c0, int c1,
+           int t0, int t1, uptr E, int64_t M, int k, int dtype, uptr out, int pooling,
+           int pooling2, uptr status, uptr stream) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_hybrid_score_rows_pool2(P<const int32_t>(idx), B, ncols, ucol,
+                                              icol, c0, c1, t0, t1, P<const void>(E),
+                                              M, k, dtype, P<float>(out), pooling, pooling2,
+                                              P<int32_t>(status), P<void>(stream));
+          }
+          check(rc, "hhfm_hybrid_score_rows_pool2");
+        });
+
+  m.def("catalog_topk_pool2",
+        [](uptr qidx, int64_t B, int ncols, int mode, int ucol, int c0, int c1,
+           int t0, int t1, uptr E, int64_t M, int k, int dtype, uptr w,
+           int item_row_begin, int item_count, int global_item_base, int K,
+           uptr top_score, uptr top_idx, uptr ws, size_t ws_bytes, int plan, int pooling,
+           int pooling2, uptr status, uptr stream) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_catalog_topk_pool2(
+                P<const int32_t>(qidx), B, ncols, mode, ucol, c0, c1, t0, t1,
+                P<const void>(E), M, k, dtype, P<const float>(w),
+                item_row_begin, item_count, global_item_base, K,
+                P<float>(top_score), P<int32_t>(top_idx), P<void>(ws), ws_bytes, plan,
+                pooling, pooling2, P<int32_t>(status), P<void>(stream));
+          }
+          check(rc, "hhfm_catalog_topk_pool2");
+        });
+
+  m.def("hhfm_train_step_pool2",
+        [](uptr X, uptr Neg, int64_t B, int ncols, int c0, int c1, int t0, int t1, int NG,
+           uptr E, int64_t M, int k, float lr, float lam, int opt, uptr accE, uptr ws,
+           size_t ws_bytes, int pooling, int pooling2, uptr loss, uptr stream) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_hhfm_train_step_pool2(P<const int32_t>(X), P<const int32_t>(Neg), B, ncols,
+                                            c0, c1, t0, t1, NG, P<float>(E), M, k, lr, lam, opt,
+                                            P<float>(accE), P<void>(ws), ws_bytes, pooling,
+                                            pooling2, P<float>(loss), P<void>(stream));
+          }
+          check(rc, "hhfm_hhfm_train_step_pool2");
+        });
+
   m.def("catalog_topk_workspace",
         [](int64_t B, int item_count, int k, int K) {
           size_t ws = 0;

@@ -310,6 +310,121 @@ __global__ __launch_bounds__(256) void hhfm_train_rows_pool(
   }
 }
 
+// Two-way HHFM (include/hhfm.h "Two-way pooling"): hhfm_train_rows_pool with
+// the forward's h from two_way_h of hhfm_pool.h (the scoring kernels' h bit
+// for bit).  On the way back dh_e reaches the stack members through H1
+// (pool_grad) and through every member product of H2 (a product sends d·s_n
+// to s_m and d·s_m to s_n); each mix's gradient reaches its rows through P1
+// and through every pair product of P2 the same way.  A max pool's ties are
+// found by re-forming the fp32 values with the forward's own expressions
+// (pool_mul), so the equality tests see the forward's bits.  One atomicAdd
+// per (row occurrence, column) carries that occurrence's summed contribution.
+// The BPR part — reduce_max over the negatives with ties split, g, gt — and
+// the loss are hhfm_train_rows's.
+__global__ __launch_bounds__(256) void hhfm_train_rows_two_way(
+    const int32_t* __restrict__ X, const int32_t* __restrict__ Neg, int64_t B, int ncols,
+    int c0, int c1, int t0, int t1, int NG, const float* __restrict__ E, int64_t M, int k,
+    PoolModes2 pm, float* __restrict__ dE, float* __restrict__ scal) {
+  const int l = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const int nc = c1 > c0 ? c1 - c0 : 0, ntm = t1 > t0 ? t1 - t0 : 0;
+  const int members = 1 + (nc > 0) + (ntm > 0);       // 2 or 3 (two_way_shape_ok)
+  for (int64_t b = wave; b < B; b += nwave) {
+    const int32_t* x = X + b * ncols;
+    const int32_t* ng = Neg + b * NG;
+    const int64_t iu = clamp_id(x[0], M), ii = clamp_id(x[1], M);
+    auto row = [&](int j, int c) { return E[(int64_t)clamp_id(x[j], M) * k + c]; };
+    auto fwd = [&](int c) {
+      return two_way_h(
+          E[iu * k + c], [&](int i) { return row(c0 + i, c); }, nc,
+          [&](int i) { return row(t0 + i, c); }, ntm, pm);
+    };
+    float pos = 0.f;
+    for (int c = l; c < k; c += kWave) pos += fwd(c).h * E[ii * k + c];
+    pos = group_sum<kWave>(pos);                        // PositiveFeadback  :171
+    float negv[kMaxNeg];
+    float mx = -__builtin_huge_valf();
+#pragma unroll
+    for (int j = 0; j < kMaxNeg; ++j) {
+      negv[j] = -__builtin_huge_valf();
+      if (j < NG) {
+        float v = 0.f;
+        const int64_t in = clamp_id(ng[j], M);
+        for (int c = l; c < k; c += kWave) v += fwd(c).h * E[in * k + c];
+        v = group_sum<kWave>(v);
+        negv[j] = v;
+        mx = fmaxf(mx, v);
+      }
+    }
+    int nt = 0;
+#pragma unroll
+    for (int j = 0; j < kMaxNeg; ++j) nt += (j < NG && negv[j] == mx);
+    const float z = pos - mx;
+    const float sg = 1.f / (1.f + expf(-z));
+    const float g = sg - 1.f;                           // d(-log σ(z))/dz      :178
+    const float gt = g / (float)nt;
+    // the gradient of one mix (value w, gradient d) towards its n rows [j0, j0 + n)
+    auto mix_back = [&](int c, const Mix2& w, float d, int j0, int n, int m1, int m2) {
+      const int np = n * (n - 1) / 2;
+      int eq1 = 0, eq2 = 0;
+      for (int i = 0; i < n; ++i) {
+        const float ri = row(j0 + i, c);
+        eq1 += ri == w.p1;
+        for (int j = i + 1; j < n; ++j) eq2 += pool_mul(ri, row(j0 + j, c)) == w.p2;
+      }
+      for (int i = 0; i < n; ++i) {
+        const float ri = row(j0 + i, c);
+        float acc = pool_grad(m1, d, ri, w.p1, eq1, n);
+        for (int j = 0; j < n; ++j) {
+          if (j == i) continue;
+          const float rj = row(j0 + j, c);
+          acc += pool_grad(m2, d, pool_mul(ri, rj), w.p2, eq2, np) * rj;
+        }
+        atomicAdd(dE + (int64_t)clamp_id(x[j0 + i], M) * k + c, acc);
+      }
+    };
+    for (int c = l; c < k; c += kWave) {
+      const TwoWay w = fwd(c);
+      const float u = E[iu * k + c];
+      const float it = E[ii * k + c];
+      float nsum = 0.f;
+#pragma unroll
+      for (int j = 0; j < kMaxNeg; ++j)
+        if (j < NG && negv[j] == mx) nsum += E[(int64_t)clamp_id(ng[j], M) * k + c];
+      const float dh = g * it - gt * nsum;
+      atomicAdd(dE + ii * k + c, g * w.h);
+#pragma unroll
+      for (int j = 0; j < kMaxNeg; ++j)
+        if (j < NG && negv[j] == mx) atomicAdd(dE + (int64_t)clamp_id(ng[j], M) * k + c, -gt * w.h);
+      // the stack: s0 = u, then mix_c, then mix_t; h = H1 + H2 sends dh to both
+      const float sc = w.c.mix, st = w.t.mix;
+      const int feq = (u == w.h1) + (nc > 0 && sc == w.h1) + (ntm > 0 && st == w.h1);
+      float du = pool_grad(pm.one.fin, dh, u, w.h1, feq, members);
+      float dc = nc > 0 ? pool_grad(pm.one.fin, dh, sc, w.h1, feq, members) : 0.f;
+      float dt = ntm > 0 ? pool_grad(pm.one.fin, dh, st, w.h1, feq, members) : 0.f;
+      if (members == 3) {
+        const float p01 = pool_mul(u, sc), p02 = pool_mul(u, st), p12 = pool_mul(sc, st);
+        const int e2 = (p01 == w.h2) + (p02 == w.h2) + (p12 == w.h2);
+        const float g01 = pool_grad(pm.two.fin, dh, p01, w.h2, e2, 3);
+        const float g02 = pool_grad(pm.two.fin, dh, p02, w.h2, e2, 3);
+        const float g12 = pool_grad(pm.two.fin, dh, p12, w.h2, e2, 3);
+        du += g01 * sc + g02 * st;
+        dc += g01 * u + g12 * st;
+        dt += g02 * u + g12 * sc;
+      } else {                                          // one product: H2 = u · s under every mode
+        const float s = nc > 0 ? sc : st;
+        du += dh * s;
+        if (nc > 0) dc += dh * u; else dt += dh * u;
+      }
+      atomicAdd(dE + iu * k + c, du);
+      if (nc > 0) mix_back(c, w.c, dc, c0, nc, pm.one.ctx, pm.two.ctx);
+      if (ntm > 0) mix_back(c, w.t, dt, t0, ntm, pm.one.tim, pm.two.tim);
+    }
+    if (l == 0) atomicAdd(scal + kScalDataLoss, -logf(sg));
+  }
+}
+
 // One TF-1.x optimizer step on a variable (training_ops.cc semantics, fp32):
 //   Adagrad   accum += g²; var -= lr·g·rsqrt(accum)           (ApplyAdagrad)
 //   SGD       var -= lr·g                                      (ApplyGradientDescent)
@@ -2259,9 +2374,18 @@ static int hhfm_train_step_impl(const int32_t* X, const int32_t* Neg, int64_t B,
                                 int32_t k, float lr, float lam, int32_t optimizer, float* accE,
                                 void* workspace, size_t ws_bytes, bool det, void* scratch,
                                 size_t scratch_bytes, float* loss, void* stream,
-                                int32_t pooling = 0) {
+                                int32_t pooling = 0, bool two_way = false,
+                                int32_t pooling2 = 0) {
   PoolModes pm;
+  PoolModes2 pm2{};
   if (!pooling_unpack(pooling, pm) || (pooling != 0 && det)) return HHFM_EINVAL;
+  if (two_way) {   // no deterministic two-way step; the layouts of two_way_shape_ok only
+    if (det || !pooling2_unpack(pooling, pooling2, pm2)) return HHFM_EINVAL;
+    if (ctx_begin > ctx_end || time_begin > time_end || ctx_begin < 0 || time_begin < 0 ||
+        ctx_end > ncols || time_end > ncols ||
+        !two_way_shape_ok(ctx_end - ctx_begin, time_end - time_begin))
+      return HHFM_EINVAL;
+  }
   if (B < 0 || ncols < 2 || NG < 1 || k < 1 || features_M < 1) return HHFM_EINVAL;
   if (NG > kMaxNeg) return HHFM_EUNSUPPORTED;
   if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
@@ -2281,7 +2405,11 @@ static int hhfm_train_step_impl(const int32_t* X, const int32_t* Neg, int64_t B,
   float* ws = reinterpret_cast<float*>(workspace);
   float* scal = ws + p.off_scal;
   char* sc = reinterpret_cast<char*>(scratch);
-  if (B > 0 && pooling != 0) {
+  if (B > 0 && two_way) {
+    hipLaunchKernelGGL(hhfm_train_rows_two_way, dim3(grid_for_n(B * 64)), dim3(256), 0, st, X,
+                       Neg, B, ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E, features_M,
+                       k, pm2, ws + p.off_dE, scal);
+  } else if (B > 0 && pooling != 0) {
     hipLaunchKernelGGL(hhfm_train_rows_pool, dim3(grid_for_n(B * 64)), dim3(256), 0, st, X, Neg,
                        B, ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E, features_M, k,
                        pm, ws + p.off_dE, scal);
@@ -2331,6 +2459,18 @@ extern "C" int hhfm_hhfm_train_step_pool(const int32_t* X, const int32_t* Neg, i
   return hhfm_train_step_impl(X, Neg, B, ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E,
                               features_M, k, lr, lam, optimizer, accE, workspace, ws_bytes, false,
                               nullptr, 0, loss, stream, pooling);
+}
+
+extern "C" int hhfm_hhfm_train_step_pool2(const int32_t* X, const int32_t* Neg, int64_t B,
+                                          int32_t ncols, int32_t ctx_begin, int32_t ctx_end,
+                                          int32_t time_begin, int32_t time_end, int32_t NG,
+                                          float* E, int64_t features_M, int32_t k, float lr,
+                                          float lam, int32_t optimizer, float* accE,
+                                          void* workspace, size_t ws_bytes, int32_t pooling,
+                                          int32_t pooling2, float* loss, void* stream) {
+  return hhfm_train_step_impl(X, Neg, B, ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E,
+                              features_M, k, lr, lam, optimizer, accE, workspace, ws_bytes, false,
+                              nullptr, 0, loss, stream, pooling, true, pooling2);
 }
 
 extern "C" int hhfm_hhfm_train_step_det(const int32_t* X, const int32_t* Neg, int64_t B,

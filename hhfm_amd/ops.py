@@ -180,17 +180,27 @@ def hybrid_score_rows(idx: torch.Tensor, E: torch.Tensor, user_col: int = 0,
                       time: Tuple[int, int] = (0, 0),
                       out: Optional[torch.Tensor] = None,
                       status: Optional[torch.Tensor] = None,
-                      pooling=None) -> torch.Tensor:
+                      pooling=None, pooling2=None) -> torch.Tensor:
     """OUR.PositiveFeadback (OurModel7.py:105-171) for rows ``idx`` -> [B].
     ``pooling``: (ctx, time, final) modes, "sum" / "max" / "mean" or POOL_*
-    (OurModel7.py:14-19 Pooling1C / 1T / 1F); None is sum pooling."""
+    (OurModel7.py:14-19 Pooling1C / 1T / 1F); None is sum pooling.
+    ``pooling2``: None is the one-way model; a (ctx, time, final) triple
+    (Pooling2C / 2T / 2F) selects the two-way model (include/hhfm.h "Two-way
+    pooling"), also when ``pooling`` is all-sum or None."""
     _idx(idx, "idx")
     dev = _need_cuda(idx, E, out)
     B, ncols = idx.shape
     M, k = E.shape
     word = pooling_word(pooling)
+    word2 = pooling_word(pooling2)
     if out is None:
         out = torch.empty(B, dtype=torch.float32, device=dev)
+    if pooling2 is not None:
+        native().hybrid_score_rows_pool2(idx.data_ptr(), B, ncols, user_col, item_col,
+                                         ctx[0], ctx[1], time[0], time[1], E.data_ptr(), M, k,
+                                         _dtype_code(E), out.data_ptr(), word, word2,
+                                         _status_ptr(status), _stream(dev))
+        return out
     if pooling is not None:
         native().hybrid_score_rows_pool(idx.data_ptr(), B, ncols, user_col, item_col,
                                         ctx[0], ctx[1], time[0], time[1], E.data_ptr(), M, k,
@@ -236,23 +246,33 @@ def catalog_topk(qidx: torch.Tensor, E: torch.Tensor, mode: int, K: int,
                  item_row_begin: int, item_count: int, global_item_base: int = 0,
                  w: Optional[torch.Tensor] = None, user_col: int = 0,
                  ctx: Tuple[int, int] = (0, 0), time: Tuple[int, int] = (0, 0),
-                 status: Optional[torch.Tensor] = None, plan: int = 0, pooling=None
-                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+                 status: Optional[torch.Tensor] = None, plan: int = 0, pooling=None,
+                 pooling2=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Full-catalog score + top-K (FM.topk FM.py:172-198, OUR.topk
     OurModel7.py:229-307). Returns (scores float32 [B,K], ids int32 [B,K]).
     ``plan``: PLAN_* flags (PLAN_EXACT_FP32, _NO_SEED, _NO_RING, _RING_ALT,
-    _GEMM, _ONE_WAVE).  ``pooling``: as in :func:`hybrid_score_rows`
-    (MODE_HHFM only)."""
+    _GEMM, _ONE_WAVE).  ``pooling`` / ``pooling2``: as in
+    :func:`hybrid_score_rows` (MODE_HHFM only; the two-way model never takes
+    the small-catalog fused kernel)."""
     _idx(qidx, "qidx")
     dev = _need_cuda(qidx, E, w)
     B, ncols = qidx.shape
     M, k = E.shape
     word = pooling_word(pooling)
+    word2 = pooling_word(pooling2)
     nat = native()
     st = _stream(dev)
     ws = _catalog_workspace(dev, st, nat.catalog_topk_workspace(B, item_count, k, K))
     top_s = torch.empty(B, K, dtype=torch.float32, device=dev)
     top_i = torch.empty(B, K, dtype=torch.int32, device=dev)
+    if pooling2 is not None:
+        nat.catalog_topk_pool2(qidx.data_ptr(), B, ncols, mode, user_col, ctx[0], ctx[1],
+                               time[0], time[1], E.data_ptr(), M, k, _dtype_code(E),
+                               0 if w is None else w.data_ptr(), item_row_begin, item_count,
+                               global_item_base, K, top_s.data_ptr(), top_i.data_ptr(),
+                               ws.data_ptr(), ws.numel(), int(plan), word, word2,
+                               _status_ptr(status), st)
+        return top_s, top_i
     if pooling is not None:
         nat.catalog_topk_pool(qidx.data_ptr(), B, ncols, mode, user_col, ctx[0], ctx[1],
                               time[0], time[1], E.data_ptr(), M, k, _dtype_code(E),

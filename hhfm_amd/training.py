@@ -185,6 +185,10 @@ def hhfm_partial_fit(model, data) -> float:
     """OUR.partial_fit (OurModel7.py:219-228): data X [B,2], Y [B,NG] negatives,
     F1 ctx columns, F2 time columns."""
     pooling = getattr(model, "pooling", None)
+    pooling2 = getattr(model, "pooling2", None)
+    if pooling2 is not None and getattr(model, "deterministic", False):
+        raise NotImplementedError("deterministic=True has no two-way step yet "
+                                  "(hhfm_hhfm_train_step_det is one-way sum pooling only)")
     if pooling is not None and getattr(model, "deterministic", False):
         raise NotImplementedError("deterministic=True has no MAX / MEAN pooled step yet "
                                   "(hhfm_hhfm_train_step_det is sum pooling only)")
@@ -207,7 +211,10 @@ def hhfm_partial_fit(model, data) -> float:
             float(model.lamda_bilinear), opt, st["feature_embeddings"].data_ptr(),
             st["ws"].data_ptr(), st["ws"].numel())
     tail = (st["loss"].data_ptr(), ops._stream(model.device))
-    if pooling is not None:
+    if pooling2 is not None:
+        native().hhfm_train_step_pool2(*args, ops.pooling_word(pooling),
+                                       ops.pooling_word(pooling2), *tail)
+    elif pooling is not None:
         native().hhfm_train_step_pool(*args, ops.pooling_word(pooling), *tail)
     elif getattr(model, "deterministic", False):
         occ = 2 + NG + (ctx[1] - ctx[0]) + (tim[1] - tim[0])   # item, negatives, user, fields

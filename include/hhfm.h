@@ -181,7 +181,8 @@ int hhfm_hybrid_score_rows_ex(const int32_t* idx, int64_t B, int32_t ncols,
  * Pooling — MAX and MEAN beside SUM for the three live pools of the reference
  * (OurModel7.py:14-19: Pooling1C over the context rows :124 / :255, Pooling1T
  * over the time rows :141 / :267, Pooling1F over the stack {user, context
- * pool, time pool} :168 / :292; its Pooling2* results are never used).
+ * pool, time pool} :168 / :292; its Pooling2* results are used by "Two-way
+ * pooling" below alone).
  * The *_pool entry points below are pure additions: every earlier entry point
  * keeps its signature and behaviour, so HHFM_ABI_VERSION stays 6.
  *
@@ -215,6 +216,60 @@ int hhfm_hybrid_score_rows_pool(const int32_t* idx, int64_t B, int32_t ncols,
                                 const void* E, int64_t features_M, int32_t k,
                                 int32_t dtype, float* out, int32_t pooling,
                                 int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Two-way pooling — the reference's second level of hybrid feature
+ * (OurModel7.py:113-122 mixdouble_features_context, :130-139
+ * mixdouble_features_time, :157-166 hybrid_feature2d, pooled by Pooling2C /
+ * Pooling2T / Pooling2F) with the three additions its committed text comments
+ * out as "#2-way stack hybrid feature" (:124, :141, :168; topk :255, :267,
+ * :292) put back.  The entry points above never form these: there the
+ * Pooling2* results stay unused.  The *_pool2 entry points are pure
+ * additions; HHFM_ABI_VERSION stays 6.
+ *
+ * Per element e, in fp32.  Each product is one rounded multiply, never
+ * contracted into an FMA with the add that follows it (its value is compared
+ * by a max pool, selected, and re-formed in the backward pass).
+ *   context   rows r_0 .. r_{nc-1} in column order.  P1 = the context pool of
+ *             "Pooling" above by `pooling`'s ctx mode.  Pairs (i, j), i < j,
+ *             i outer (the reference's loop order), p_ij = r_i · r_j; P2 = the
+ *             pool of the nc(nc-1)/2 products in that order by `pooling2`'s
+ *             ctx mode, through the same identity / step / finish (mean: the
+ *             sum, then one division by the number of products).
+ *             mix_c = P1 + P2 (one add).
+ *   time      the same over the nt time rows by the two words' time modes.
+ *   stack     members s_0 = u, then mix_c if nc > 0, then mix_t if nt > 0.
+ *             H1 = the final pool of "Pooling" over them by `pooling`'s final
+ *             mode; H2 = the pool by `pooling2`'s final mode of the member
+ *             products in the order (0,1), (0,2), (1,2).
+ *   h         H1 + H2 (one add);  score = Σ_e h_e · item_e.
+ * `pooling2` packs its three modes exactly like `pooling` (HHFM_POOLING); all
+ * 27 x 27 combinations are legal, a stray bit or a mode of 3 in either word is
+ * HHFM_EINVAL.  pooling2 == 0 (sum, sum, sum) is still the two-way model — a
+ * different model from the one-way one — so "off" is not a value of the word:
+ * the one-way model is the entry points above.
+ * Refused shapes (HHFM_EINVAL, nothing written): a present pool of exactly
+ * one row (nc == 1 or nt == 1) and a stack of one member (nc == nt == 0); the
+ * reference's graph cannot be built for them either (it stacks an empty list
+ * at :119 / :136 / :163).
+ * Gradients follow TF's: a product sends d·r_j to r_i and d·r_i to r_j (an id
+ * that occurs twice receives both); the pools of both levels use the rules of
+ * hhfm_hhfm_train_step_pool — sum d, mean d / n, max d shared among the
+ * values bit-equal to the maximum.
+ * (csrc/hhfm_pool.h two_way_h is the one device implementation; numpy
+ * restatement in tests/hhfm_two_way_ref.py.)
+ * Not built: a two-way form of the small-catalog fused kernel,
+ * a deterministic two-way step, two-way on bf16 training tables.
+ * ---------------------------------------------------------------------- */
+/* H1, two-way (the arguments of hhfm_hybrid_score_rows_pool, with `pooling2`
+ * after `pooling`). */
+int hhfm_hybrid_score_rows_pool2(const int32_t* idx, int64_t B, int32_t ncols,
+                                 int32_t user_col, int32_t item_col,
+                                 int32_t ctx_begin, int32_t ctx_end,
+                                 int32_t time_begin, int32_t time_end,
+                                 const void* E, int64_t features_M, int32_t k,
+                                 int32_t dtype, float* out, int32_t pooling,
+                                 int32_t pooling2, int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------------
  * M2/H2 — full-catalog score + fused top-K (replaces FM.topk, FM.py:172-198,
@@ -282,6 +337,21 @@ int hhfm_catalog_topk_pool(const int32_t* qidx, int64_t B, int32_t ncols,
                            float* top_score, int32_t* top_idx, void* workspace,
                            size_t ws_bytes, int32_t plan, int32_t pooling,
                            int32_t* status, void* stream);
+/* Same, two-way ("Two-way pooling" above; `pooling2` after `pooling`):
+ * HHFM_MODE_HHFM only (HHFM_MODE_FM is HHFM_EINVAL).  The workspace query is
+ * unchanged.  The query vector h is always formed by its own query kernel and
+ * the main kernels (score matrix, seed, ring, merges) then run unchanged; the
+ * small-catalog fused kernel is never taken — a two-way form of it is not
+ * built — so HHFM_PLAN_FUSED has no effect here. */
+int hhfm_catalog_topk_pool2(const int32_t* qidx, int64_t B, int32_t ncols,
+                            int32_t mode, int32_t user_col, int32_t ctx_begin,
+                            int32_t ctx_end, int32_t time_begin, int32_t time_end,
+                            const void* E, int64_t features_M, int32_t k,
+                            int32_t dtype, const float* w, int32_t item_row_begin,
+                            int32_t item_count, int32_t global_item_base, int32_t K,
+                            float* top_score, int32_t* top_idx, void* workspace,
+                            size_t ws_bytes, int32_t plan, int32_t pooling,
+                            int32_t pooling2, int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------------
  * Top-K merge of R sorted partial lists per query (the item-sharded
@@ -513,6 +583,17 @@ int hhfm_hhfm_train_step_pool(const int32_t* X, const int32_t* Neg, int64_t B, i
                               int32_t k, float lr, float lambda_l2, int32_t optimizer,
                               float* accE, void* workspace, size_t ws_bytes, int32_t pooling,
                               float* loss, void* stream);
+/* The two-way step ("Two-way pooling" above; `pooling2` after `pooling`): the
+ * forward's h is the two-way one, the backward sends dh_e through H1 and H2
+ * to the stack members and each mix's gradient through P1 and every pair
+ * product to the rows.  Same workspace, BPR part, optimizer tail and loss;
+ * fp32 tables, not deterministic. */
+int hhfm_hhfm_train_step_pool2(const int32_t* X, const int32_t* Neg, int64_t B, int32_t ncols,
+                               int32_t ctx_begin, int32_t ctx_end, int32_t time_begin,
+                               int32_t time_end, int32_t NG, float* E, int64_t features_M,
+                               int32_t k, float lr, float lambda_l2, int32_t optimizer,
+                               float* accE, void* workspace, size_t ws_bytes, int32_t pooling,
+                               int32_t pooling2, float* loss, void* stream);
 
 /* Training dropout (`--keep` < 1 of FM.py:42-43, AFM.py:43-44).  The
  * arithmetic and the gradient are tf.nn.dropout's (TF 1.x):

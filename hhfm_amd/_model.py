@@ -1,4 +1,4 @@
-"""Shared plumbing of the model classes (FM, OUR, AFM, DeepFM).
+"""Shared plumbing of the model classes (FM, OUR, AFM, DeepFM, CARS2).
 
 Each reference model is a TF-1.x graph plus ``sess.run`` (e.g. FM.py:81-148);
 here a model owns its weights as device tensors and scores through the HIP

@@ -21,6 +21,7 @@
 //  3. topk_merge: per query, merge the S split lists (and, multi-GPU, the R
 //     rank lists gathered over RCCL) into the final top-K.
 // Order everywhere: score descending, item index ascending (tf.nn.top_k).
+#include "cars2.h"
 #include "gemm_mfma.h"
 #include "hhfm_pool.h"
 
@@ -1478,7 +1479,8 @@ static int catalog_topk_impl(
     int32_t dtype, const float* w, int32_t item_row_begin, int32_t item_count,
     int32_t global_item_base, int32_t K, float* top_score, int32_t* top_idx,
     void* workspace, size_t ws_bytes, int32_t plan, int32_t pooling, int32_t* status,
-    void* stream, bool two_way = false, int32_t pooling2 = 0) {
+    void* stream, bool two_way = false, int32_t pooling2 = 0,
+    const Cars2Query* cars2 = nullptr) {
   PoolModes pm;
   PoolModes2 pm2{};
   if (!pooling_unpack(pooling, pm)) return HHFM_EINVAL;
@@ -1519,7 +1521,7 @@ static int catalog_topk_impl(
   int32_t* gthr = reinterpret_cast<int32_t*>(ws + p.off_thr);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const char* Eb = reinterpret_cast<const char*>(E);
-  {
+  if (!cars2) {   // (cars2_queries checks its two id ranges itself)
     const int rc = launch_check_query_ids(qidx, B, ncols, user_col, ctx_begin, ctx_end,
                                           time_begin, time_end, features_M, status, st);
     if (rc != HHFM_OK) return rc;
@@ -1532,7 +1534,7 @@ static int catalog_topk_impl(
   // (two-way has no form of the fused kernel: it always forms H with
   // catalog_queries_two_way and runs the main kernels below)
   const bool fused_size = item_count <= 8192 || (plan & HHFM_PLAN_FUSED);
-  if (!two_way && p.dense && fused_size && K <= 32 && KT <= 8 && p.fS <= kFusedMaxS &&
+  if (!two_way && !cars2 && p.dense && fused_size && K <= 32 && KT <= 8 && p.fS <= kFusedMaxS &&
       (B + kQPerWave - 1) / kQPerWave <= kFusedMaxGroups &&
       ctx_end - ctx_begin <= kFusedMaxCtx && time_end - time_begin <= kFusedMaxCtx &&
       !(plan & (HHFM_PLAN_GEMM | HHFM_PLAN_STORE))) {
@@ -1558,7 +1560,9 @@ static int catalog_topk_impl(
   {
     int64_t blocks = (p.Bpad + 3) / 4;
     if (blocks > 4096) blocks = 4096;
-    if (two_way && bf16)
+    if (cars2)   // CARS2: h = u + GB[m], cst = u·GA[m]; the main kernels' FM form with w = NULL
+      cars2_launch_queries(qidx, B, p.Bpad, Eb, bf16, features_M, k, *cars2, H, cst, status, st);
+    else if (two_way && bf16)
       hipLaunchKernelGGL(catalog_queries_two_way<true>, dim3((int)blocks), dim3(256), 0, st,
                          qidx, B, p.Bpad, ncols, user_col, ctx_begin, ctx_end, time_begin,
                          time_end, Eb, features_M, k, pm2, H, cst);
@@ -1733,6 +1737,23 @@ extern "C" int hhfm_catalog_topk_pool2(
                            time_end, E, features_M, k, dtype, w, item_row_begin, item_count,
                            global_item_base, K, top_score, top_idx, workspace, ws_bytes, plan,
                            pooling, status, stream, true, pooling2);
+}
+
+// CARS2.topk (CARS2.py:171-187; include/hhfm.h "CARS2"): H and cst from
+// cars2_queries (cars2.hip), then the main kernels unchanged on their FM form
+// with w = NULL, so that cst is added; never the small-catalog fused kernel.
+extern "C" int hhfm_cars2_catalog_topk(
+    const int32_t* q, int64_t B, const void* UI, int64_t n_ui, int32_t D, int32_t dtype,
+    const void* prepared, int64_t Mc, int32_t item_row_begin, int32_t item_count,
+    int32_t global_item_base, int32_t K, float* top_score, int32_t* top_idx, void* workspace,
+    size_t ws_bytes, int32_t plan, int32_t* status, void* stream) {
+  if (Mc < 1 || D < 1) return HHFM_EINVAL;
+  if (B > 0 && !prepared) return HHFM_EINVAL;
+  const float* GA = reinterpret_cast<const float*>(prepared);
+  const Cars2Query cq{GA, GA + Mc * D, Mc};
+  return catalog_topk_impl(q, B, 2, HHFM_MODE_FM, 0, 0, 0, 0, 0, UI, n_ui, D, dtype, nullptr,
+                           item_row_begin, item_count, global_item_base, K, top_score, top_idx,
+                           workspace, ws_bytes, plan, 0, status, stream, false, 0, &cq);
 }
 
 #if HHFM_FUSED_TIMING

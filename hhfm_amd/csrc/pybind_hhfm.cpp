@@ -195,6 +195,93 @@ PYBIND11_MODULE(_hhfm, m) {
           check(rc, "hhfm_hhfm_train_step_pool2");
         });
 
+  // CARS2 (include/hhfm.h "CARS2")
+  m.def("cars2_prepared_bytes", [](int64_t Mc, int D, int Dc) {
+    size_t n = 0;
+    check(hhfm_cars2_prepared_bytes(Mc, D, Dc, &n), "hhfm_cars2_prepared_bytes");
+    return n;
+  });
+
+  m.def("cars2_prepare",
+        [](uptr Context, int64_t Mc, uptr W, uptr A, uptr Z, uptr Bv, int D, int Dc, int Dp,
+           int Dq, uptr prepared, size_t prepared_bytes, uptr stream) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_cars2_prepare(P<const float>(Context), Mc, P<const float>(W),
+                                    P<const float>(A), P<const float>(Z), P<const float>(Bv), D,
+                                    Dc, Dp, Dq, P<void>(prepared), prepared_bytes,
+                                    P<void>(stream));
+          }
+          check(rc, "hhfm_cars2_prepare");
+        });
+
+  m.def("cars2_score_rows",
+        [](uptr idx, int64_t B, uptr UI, int64_t n_ui, int D, int dtype, uptr prepared,
+           int64_t Mc, uptr out, uptr status, uptr stream) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_cars2_score_rows(P<const int32_t>(idx), B, P<const void>(UI), n_ui, D,
+                                       dtype, P<const void>(prepared), Mc, P<float>(out),
+                                       P<int32_t>(status), P<void>(stream));
+          }
+          check(rc, "hhfm_cars2_score_rows");
+        });
+
+  m.def("cars2_catalog_topk",
+        [](uptr q, int64_t B, uptr UI, int64_t n_ui, int D, int dtype, uptr prepared, int64_t Mc,
+           int item_row_begin, int item_count, int global_item_base, int K, uptr top_score,
+           uptr top_idx, uptr ws, size_t ws_bytes, int plan, uptr status, uptr stream) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_cars2_catalog_topk(P<const int32_t>(q), B, P<const void>(UI), n_ui, D,
+                                         dtype, P<const void>(prepared), Mc, item_row_begin,
+                                         item_count, global_item_base, K, P<float>(top_score),
+                                         P<int32_t>(top_idx), P<void>(ws), ws_bytes, plan,
+                                         P<int32_t>(status), P<void>(stream));
+          }
+          check(rc, "hhfm_cars2_catalog_topk");
+        });
+
+  m.def("cars2_train_workspace",
+        [](int64_t B, int64_t n_ui, int64_t Mc, int D, int Dc, int Dp, int Dq) {
+          size_t ws = 0;
+          check(hhfm_cars2_train_workspace(B, n_ui, Mc, D, Dc, Dp, Dq, &ws),
+                "hhfm_cars2_train_workspace");
+          return ws;
+        });
+
+  m.def("cars2_train_state_bytes", [](int64_t n_ui, int64_t Mc, int D, int Dc, int Dp, int Dq) {
+    size_t n = 0;
+    check(hhfm_cars2_train_state_bytes(n_ui, Mc, D, Dc, Dp, Dq, &n),
+          "hhfm_cars2_train_state_bytes");
+    return n;
+  });
+
+  m.def("cars2_train_step",
+        [](uptr X, uptr Fea, uptr Neg, int64_t B, int NG, uptr UI, int64_t n_ui, uptr Context,
+           int64_t Mc, uptr W, uptr Z, uptr A, uptr Bv, int D, int Dc, int Dp, int Dq, float lr,
+           float lam, int opt, std::vector<uptr> acc, uptr ws, size_t ws_bytes, uptr loss,
+           uptr stream) {
+          if (opt != HHFM_OPT_SGD && acc.size() != 6)
+            throw py::value_error("acc needs 6 slot arrays (UI, Context, W, Z, A, B)");
+          std::vector<float*> av(acc.size());
+          for (size_t i = 0; i < acc.size(); ++i) av[i] = P<float>(acc[i]);
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_cars2_train_step(P<const int32_t>(X), P<const int32_t>(Fea),
+                                       P<const int32_t>(Neg), B, NG, P<float>(UI), n_ui,
+                                       P<float>(Context), Mc, P<float>(W), P<float>(Z),
+                                       P<float>(A), P<float>(Bv), D, Dc, Dp, Dq, lr, lam, opt,
+                                       av.empty() ? nullptr : av.data(), P<void>(ws), ws_bytes,
+                                       P<float>(loss), P<void>(stream));
+          }
+          check(rc, "hhfm_cars2_train_step");
+        });
+
   m.def("catalog_topk_workspace",
         [](int64_t B, int item_count, int k, int K) {
           size_t ws = 0;

@@ -19,6 +19,8 @@
 //                         DeepFM's reuse their default kernels under a DET flag)
 //   hhfm_dfm_train_step_head / _head_det  DeepFM's FM-only, deep-only and logloss
 //                         heads (DFM.py:131-152): the DeepFM step under a head word
+//   hhfm_cars2_train_step replaces the same for CARS2 (Newcode/CARS2.py:87,
+//                         :103-136, :167-170); its kernels are in cars2.hip
 //
 // One wave per batch row computes the forward score(s) and scatters the
 // gradient of the row's loss into dense fp32 gradient buffers with float
@@ -44,6 +46,7 @@
 #include <initializer_list>
 #include <iterator>
 
+#include "cars2.h"
 #include "dropout.h"
 #include "gemm_mfma.h"
 #include "hhfm_pool.h"
@@ -598,6 +601,9 @@ struct OptVar {
   int rowlen;     // elements per table row (the touched mask's index is i / rowlen)
   bool sparse;    // the variable's TF gradient is an IndexedSlices
   bool sumsq;     // Σ var² (pre-update) goes into the loss's l2 term
+  // a sparse variable indexed by ids other than the tail's `ids` (CARS2's
+  // Context): its own touched mask, marked and cleared by the caller
+  const uint8_t* own_touched = nullptr;
 };
 
 struct IdList {
@@ -628,7 +634,8 @@ static int optimizer_tail(const OptVar* vars, int nvars, std::initializer_list<I
   int64_t nss = 0;   // partials written so far
   for (int i = 0; i < nvars; ++i) {
     const OptVar& v = vars[i];
-    OptStep o{opt, lr, scal + kScalAdam, v.sparse ? touched : nullptr, v.rowlen, v.sparse ? 1 : 0};
+    const uint8_t* mask = v.own_touched ? v.own_touched : touched;
+    OptStep o{opt, lr, scal + kScalAdam, v.sparse ? mask : nullptr, v.rowlen, v.sparse ? 1 : 0};
     if (ss_part) {
       hipLaunchKernelGGL(optimizer_apply<true>, dim3(grid_for_n(v.n)), dim3(256), 0, st, v.var,
                          v.grad, v.slot, v.n, v.lam, o, v.sumsq ? ss_part + nss : nullptr);
@@ -2483,6 +2490,118 @@ extern "C" int hhfm_hhfm_train_step_det(const int32_t* X, const int32_t* Neg, in
   return hhfm_train_step_impl(X, Neg, B, ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E,
                               features_M, k, lr, lam, optimizer, accE, workspace, ws_bytes, true,
                               scratch, scratch_bytes, loss, stream);
+}
+
+// ---------------------------------------------------------------------------
+// CARS2 (Newcode/CARS2.py:87, :103-136, :167-170; include/hhfm.h "CARS2").
+// The workspace, in floats, every region on a 256-byte boundary:
+//   dUI [n_ui·D] | dContext [Mc·Dc] | dW [D·Dp·Dc] | dZ [D·Dq·Dc] | dA [Dp] |
+//   dB [Dq] | scal [kScalFloats] | touched mask of UI (n_ui bytes) | touched
+//   mask of Context (Mc bytes)                      <- the persistent prefix
+//   ZB [D·Dc] | GB [Mc·D] | T [D·Dc] | gδ [B·D]     <- per-batch scratch
+// dW and dA stay zero: the data gradient of W and A is identically zero.
+// ---------------------------------------------------------------------------
+struct Cars2TrainPlan {
+  int64_t dUI, dCtx, dW, dZ, dA, dB, scal, touchUI, touchCtx, state;
+  int64_t ZB, GB, T, gd, total;   // floats
+};
+
+static bool cars2_train_plan(int64_t B, int64_t n_ui, int64_t Mc, int D, int Dc, int Dp, int Dq,
+                             Cars2TrainPlan& p) {
+  if (B < 0 || n_ui < 1 || Mc < 1 || D < 1 || Dc < 1 || Dp < 1 || Dq < 1) return false;
+  if (n_ui > ((int64_t)1 << 31) || Mc > ((int64_t)1 << 31) || B > ((int64_t)1 << 31)) return false;
+  if ((int64_t)D * Dc * (Dp > Dq ? Dp : Dq) > ((int64_t)1 << 30)) return false;
+  int64_t o = 0;
+  auto take = [&](int64_t n) {
+    const int64_t at = o;
+    o += (n + 63) & ~int64_t(63);
+    return at;
+  };
+  p.dUI = take(n_ui * D);
+  p.dCtx = take(Mc * Dc);
+  p.dW = take((int64_t)D * Dp * Dc);
+  p.dZ = take((int64_t)D * Dq * Dc);
+  p.dA = take(Dp);
+  p.dB = take(Dq);
+  p.scal = take(kScalFloats);
+  p.touchUI = take((n_ui + 3) / 4);
+  p.touchCtx = take((Mc + 3) / 4);
+  p.state = o;
+  p.ZB = take((int64_t)D * Dc);
+  p.GB = take(Mc * D);
+  p.T = take((int64_t)D * Dc);
+  p.gd = take(B * D);
+  p.total = o;
+  return true;
+}
+
+extern "C" int hhfm_cars2_train_workspace(int64_t B, int64_t n_ui, int64_t Mc, int32_t D,
+                                          int32_t Dc, int32_t Dp, int32_t Dq, size_t* ws_bytes) {
+  Cars2TrainPlan p;
+  if (!ws_bytes || !cars2_train_plan(B, n_ui, Mc, D, Dc, Dp, Dq, p)) return HHFM_EINVAL;
+  *ws_bytes = (size_t)p.total * 4;
+  return HHFM_OK;
+}
+
+extern "C" int hhfm_cars2_train_state_bytes(int64_t n_ui, int64_t Mc, int32_t D, int32_t Dc,
+                                            int32_t Dp, int32_t Dq, size_t* state_bytes) {
+  Cars2TrainPlan p;
+  if (!state_bytes || !cars2_train_plan(1, n_ui, Mc, D, Dc, Dp, Dq, p)) return HHFM_EINVAL;
+  *state_bytes = (size_t)p.state * 4;
+  return HHFM_OK;
+}
+
+extern "C" int hhfm_cars2_train_step(const int32_t* X, const int32_t* Fea, const int32_t* Neg,
+                                     int64_t B, int32_t NG, float* UI, int64_t n_ui,
+                                     float* Context, int64_t Mc, float* W, float* Z, float* A,
+                                     float* Bv, int32_t D, int32_t Dc, int32_t Dp, int32_t Dq,
+                                     float lr, float lambda_l2, int32_t optimizer,
+                                     float* const* acc, void* workspace, size_t ws_bytes,
+                                     float* loss, void* stream) {
+  Cars2TrainPlan p;
+  if (NG < 1 || !cars2_train_plan(B, n_ui, Mc, D, Dc, Dp, Dq, p)) return HHFM_EINVAL;
+  if (NG > kMaxNeg || D > kCars2TrainMaxD) return HHFM_EUNSUPPORTED;
+  if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
+  if (!UI || !Context || !W || !Z || !A || !Bv || !loss || !workspace) return HHFM_EINVAL;
+  if (B > 0 && (!X || !Fea || !Neg)) return HHFM_EINVAL;
+  if (!slots_ok(optimizer, acc, 6)) return HHFM_EINVAL;   // acc: UI, Context, W, Z, A, B
+  if (ws_bytes < (size_t)p.total * 4) return HHFM_EWORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  float* ws = reinterpret_cast<float*>(workspace);
+  float* scal = ws + p.scal;
+  const float lam = lambda_l2 > 0.f ? lambda_l2 : 0.f;   // CARS2.py:115
+  if (B > 0) {
+    const hipError_t me = hipMemsetAsync(ws + p.T, 0, (size_t)D * Dc * 4, st);
+    if (me != hipSuccess) return (int)me;
+    cars2_launch_fold(Z, Bv, D, Dq, Dc, ws + p.ZB, st);
+    cars2_launch_table(ws + p.ZB, Context, Mc, D, Dc, ws + p.GB, st);
+    cars2_launch_train_rows(X, Fea, Neg, B, NG, UI, n_ui, D, Dc, ws + p.GB, ws + p.ZB, Mc,
+                            ws + p.dUI, ws + p.dCtx, ws + p.gd, scal + kScalDataLoss, st);
+    cars2_launch_t(ws + p.gd, Fea, Context, B, Mc, D, Dc, ws + p.T, st);
+    cars2_launch_dz_db(Z, Bv, ws + p.T, D, Dq, Dc, ws + p.dZ, ws + p.dB, st);
+  }
+  // with λ > 0 the l2 terms make every gradient dense (CARS2.py:115-121); at
+  // λ = 0 UI and Context are IndexedSlices, Z and B dense, W and A dense zeros
+  const bool sp = lam == 0.f;
+  uint8_t* touchedUI = reinterpret_cast<uint8_t*>(ws + p.touchUI);
+  uint8_t* touchedCtx = reinterpret_cast<uint8_t*>(ws + p.touchCtx);
+  const bool mark = sp && optimizer == HHFM_OPT_MOMENTUM && B > 0;
+  if (mark)
+    hipLaunchKernelGGL(mark_rows, dim3(grid_for_n(B)), dim3(256), 0, st, Fea, B, Mc, touchedCtx,
+                       (uint8_t)1);
+  const OptVar vars[] = {
+      {UI, ws + p.dUI, slot_of(optimizer, acc, 0), n_ui * D, lam, D, sp, true},
+      {Context, ws + p.dCtx, slot_of(optimizer, acc, 1), Mc * Dc, lam, Dc, sp, true, touchedCtx},
+      {W, ws + p.dW, slot_of(optimizer, acc, 2), (int64_t)D * Dp * Dc, lam, 1, false, true},
+      {Z, ws + p.dZ, slot_of(optimizer, acc, 3), (int64_t)D * Dq * Dc, lam, 1, false, true},
+      {A, ws + p.dA, slot_of(optimizer, acc, 4), Dp, lam, 1, false, true},
+      {Bv, ws + p.dB, slot_of(optimizer, acc, 5), Dq, lam, 1, false, true}};
+  const int rc = optimizer_tail(vars, (int)std::size(vars), {{X, B * 2}, {Neg, B * NG}}, n_ui,
+                                optimizer, lr, scal, touchedUI, lam, loss, st);
+  if (mark)
+    hipLaunchKernelGGL(mark_rows, dim3(grid_for_n(B)), dim3(256), 0, st, Fea, B, Mc, touchedCtx,
+                       (uint8_t)0);
+  return rc != 0 ? rc : (int)hipGetLastError();
 }
 
 extern "C" int hhfm_dfm_train_workspace(int64_t B, int32_t F, int32_t k, int64_t features_M,

@@ -289,6 +289,92 @@ def catalog_topk(qidx: torch.Tensor, E: torch.Tensor, mode: int, K: int,
     return top_s, top_i
 
 
+# ---------------------------------------------------------------------------
+# CARS2 (include/hhfm.h "CARS2")
+# ---------------------------------------------------------------------------
+def cars2_dims(hidden_factor: int) -> Tuple[int, int, int]:
+    """(Dc, Dp, Dq) of CARS2.py:54-56."""
+    D = int(hidden_factor)
+    return int(D / 2.5), int(D / 5), int(D / 2.5)
+
+
+def _cars2_f32(name, t, shape):
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be float32 {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+
+def cars2_prepare(Context: torch.Tensor, W: torch.Tensor, Z: torch.Tensor, A: torch.Tensor,
+                  B: torch.Tensor) -> torch.Tensor:
+    """hhfm_cars2_prepare: the folded tables GA | GB | WA | ZB as one float32
+    device tensor, to be passed with Mc = Context.shape[0] to
+    :func:`cars2_score_rows` / :func:`cars2_catalog_topk`; stale once Context, W, Z, A or B change."""
+    dev = _need_cuda(Context, W, Z, A, B)
+    Mc, Dc = Context.shape
+    D, Dp, _ = W.shape
+    Dq = Z.shape[1]
+    _cars2_f32("Context", Context, (Mc, Dc))
+    _cars2_f32("W", W, (D, Dp, Dc))
+    _cars2_f32("Z", Z, (D, Dq, Dc))
+    _cars2_f32("A", A, (Dp,))
+    _cars2_f32("B", B, (Dq,))
+    nat = native()
+    nbytes = nat.cars2_prepared_bytes(Mc, D, Dc)
+    prepared = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    nat.cars2_prepare(Context.data_ptr(), Mc, W.data_ptr(), A.data_ptr(), Z.data_ptr(),
+                      B.data_ptr(), D, Dc, Dp, Dq, prepared.data_ptr(), nbytes, _stream(dev))
+    return prepared
+
+
+def cars2_score_rows(idx: torch.Tensor, UI: torch.Tensor, prepared: torch.Tensor, Mc: int,
+                     out: Optional[torch.Tensor] = None,
+                     status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """CARS2.PositiveFeadback (CARS2.py:85-105) for rows ``idx`` int32 [B, 3] =
+    (user id, item id, context id) -> float32 [B]."""
+    _idx(idx, "idx")
+    if idx.shape[1] != 3:
+        raise ValueError("idx must be [rows, 3]: user id, item id, context id")
+    dev = _need_cuda(idx, UI, prepared, out)
+    B = idx.shape[0]
+    n_ui, D = UI.shape
+    Mc = int(Mc)
+    if prepared.dtype != torch.float32 or prepared.numel() < 2 * Mc * D:
+        raise ValueError("prepared must be cars2_prepare's float32 tensor for this Mc and D")
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=dev)
+    native().cars2_score_rows(idx.data_ptr(), B, UI.data_ptr(), n_ui, D, _dtype_code(UI),
+                              prepared.data_ptr(), Mc, out.data_ptr(), _status_ptr(status),
+                              _stream(dev))
+    return out
+
+
+def cars2_catalog_topk(q: torch.Tensor, UI: torch.Tensor, prepared: torch.Tensor, Mc: int, K: int,
+                       item_row_begin: int, item_count: int, global_item_base: int = 0,
+                       status: Optional[torch.Tensor] = None, plan: int = 0
+                       ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """CARS2.topk (CARS2.py:171-187) for queries ``q`` int32 [B, 2] = (user id,
+    context id) over UI rows [item_row_begin, +item_count) -> (scores float32
+    [B, K], ids int32 [B, K]); ``plan`` as in :func:`catalog_topk`."""
+    _idx(q, "q")
+    if q.shape[1] != 2:
+        raise ValueError("q must be [rows, 2]: user id, context id")
+    dev = _need_cuda(q, UI, prepared)
+    B = q.shape[0]
+    n_ui, D = UI.shape
+    Mc = int(Mc)
+    if prepared.dtype != torch.float32 or prepared.numel() < 2 * Mc * D:
+        raise ValueError("prepared must be cars2_prepare's float32 tensor for this Mc and D")
+    nat = native()
+    st = _stream(dev)
+    ws = _catalog_workspace(dev, st, nat.catalog_topk_workspace(B, item_count, D, K))
+    top_s = torch.empty(B, K, dtype=torch.float32, device=dev)
+    top_i = torch.empty(B, K, dtype=torch.int32, device=dev)
+    nat.cars2_catalog_topk(q.data_ptr(), B, UI.data_ptr(), n_ui, D, _dtype_code(UI),
+                           prepared.data_ptr(), Mc, item_row_begin, item_count,
+                           global_item_base, K, top_s.data_ptr(), top_i.data_ptr(),
+                           ws.data_ptr(), ws.numel(), int(plan), _status_ptr(status), st)
+    return top_s, top_i
+
+
 def topk_merge(scores: torch.Tensor, ids: torch.Tensor
                ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Merge R sorted [B,K] lists (stacked [R,B,K], rank-major) into [B,K].

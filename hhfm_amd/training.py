@@ -1,5 +1,5 @@
-"""Training surface (§8f "next" H6): ``partial_fit`` of FM, HHFM, DeepFM and
-AFM on the gfx950 train-step kernels and the reference's epoch loops.
+"""Training surface (§8f "next" H6): ``partial_fit`` of FM, HHFM, DeepFM, AFM
+and CARS2 on the gfx950 train-step kernels and the reference's epoch loops.
 
 * FM / AFM / DFM loop — FM.py:221-282: each epoch NG=2 negatives per
   positive (label 0 for FM, -1 for AFM/DFM, FM.py:248 / AFM.py:317), shuffle,
@@ -225,6 +225,46 @@ def hhfm_partial_fit(model, data) -> float:
     return float(st["loss"].item())
 
 
+def cars2_partial_fit(model, data) -> float:
+    """CARS2.partial_fit (CARS2.py:167-170): data X [B,2] (user, item), Y [B,NG]
+    negatives (summed, :87), F1 [B] context ids; one TF step on the six
+    variables (include/hhfm.h "CARS2")."""
+    if getattr(model, "deterministic", False):
+        raise NotImplementedError("deterministic=True has no CARS2 step "
+                                  "(hhfm_cars2_train_step sums with float atomics)")
+    opt = _opt_code(model)
+    W = model.weights
+    names = list(model.NAMES)
+    st = _state(model, names, opt)
+    X = model._idx(np.asarray(data["X"]).reshape(-1, 2), ctx_last=False)
+    Neg = model._idx(np.asarray(data["Y"]), ctx_last=False)
+    Fea = model._idx(np.asarray(data["F1"]).reshape(-1, 1))
+    B, NG = Neg.shape
+    if X.shape[0] != B or Fea.shape[0] != B:
+        raise ValueError("X, Y and F1 must have the same number of rows")
+    if model.validate and B:
+        n_ui = model.n_user + model.n_item
+        ops.validate_ids(X, n_ui)
+        ops.validate_ids(Neg, n_ui)
+        ops.validate_ids(Fea, model.features_M)
+    n_ui, D = W["UI"].shape
+    Mc, Dc = W["Context"].shape
+    Dp, Dq = W["W"].shape[1], W["Z"].shape[1]
+    nat = native()
+    ws = _ensure_ws(st, B, model.device,
+                    lambda b: nat.cars2_train_workspace(b, n_ui, Mc, D, Dc, Dp, Dq),
+                    lambda: nat.cars2_train_state_bytes(n_ui, Mc, D, Dc, Dp, Dq))
+    ptr = lambda n: W[n].data_ptr()  # noqa: E731
+    nat.cars2_train_step(X.data_ptr(), Fea.data_ptr(), Neg.data_ptr(), B, NG, ptr("UI"), n_ui,
+                         ptr("Context"), Mc, ptr("W"), ptr("Z"), ptr("A"), ptr("B"), D, Dc, Dp,
+                         Dq, float(model.learning_rate), float(model.lamda_bilinear), opt,
+                         [st[n].data_ptr() for n in names] if opt != _SGD else [],
+                         ws.data_ptr(), ws.numel(), st["loss"].data_ptr(),
+                         ops._stream(model.device))
+    model._prep = None   # the folded tables of the scoring path are stale
+    return float(st["loss"].item())
+
+
 def dfm_partial_fit(model, data) -> float:
     """DeepFM.partial_fit (DFM.py:214-217): one TF Adagrad step on every
     variable the model's head gives a gradient (DFM.py:155; without use_deep
@@ -368,34 +408,45 @@ def run_training(tr, negatives=2, neg_label=0, plateau=-0.0075, epoch_cap=100):
     return tr.loss_epoch
 
 
-def run_training_hhfm(tr):
-    """OurModel7.py:349-413."""
+def _hhfm_fields(tr, rows, batch):
+    """The context / time columns of an HHFM batch (OurModel7.py:374-385)."""
+    td = tr.time_dimension
+    if tr.context and tr.time:
+        batch["F1"] = np.array(rows[:, 2:-td], dtype=np.int64)
+        batch["F2"] = np.array(rows[:, -td:], dtype=np.int64)
+    elif tr.context:
+        batch["F1"] = np.array(rows[:, 2:], dtype=np.int64)
+    else:
+        batch["F2"] = np.array(rows[:, 2:], dtype=np.int64)
+
+
+def _cars2_fields(tr, rows, batch):
+    """The context id of a CARS2 batch (CARS2.py:249)."""
+    batch["F1"] = tr.context_ids(rows)
+
+
+def run_training_hhfm(tr, NG=10, plateau_after=20, fields=_hhfm_fields):
+    """OurModel7.py:349-413; CARS2.py:222-279 is the same loop with ``NG`` = 1,
+    the plateau rule from epoch 11 and the context id as the only field
+    (``run_training_cars2``)."""
     args = tr.args
     _report_init(tr)
     tr.loss_epoch = []
-    td = tr.time_dimension
     for epoch in range(1, tr.epoch):
         loss = 0.0
         t1 = time()
         pos = tr.data.Train_data.values[:, 1:]
         np.random.shuffle(pos)            # in place, like the reference (:369-370)
-        NG = 10
         negs = tr.sample_negative(pos, NG)
         for chunk in partition_all(tr.batch_size, range(len(pos))):
             rows = pos[chunk]
             batch = {"X": np.array(rows[:, :2], dtype=np.int64),
                      "Y": np.array(negs[chunk], dtype=np.int64)}
-            if tr.context and tr.time:
-                batch["F1"] = np.array(rows[:, 2:-td], dtype=np.int64)
-                batch["F2"] = np.array(rows[:, -td:], dtype=np.int64)
-            elif tr.context:
-                batch["F1"] = np.array(rows[:, 2:], dtype=np.int64)
-            else:
-                batch["F2"] = np.array(rows[:, 2:], dtype=np.int64)
+            fields(tr, rows, batch)
             loss = loss + tr.model.partial_fit(batch)
         tr.loss_epoch.append(loss)
         t2 = time()
-        if args.Result == 1 and epoch > 20:
+        if args.Result == 1 and epoch > plateau_after:
             n = 3
             le = np.array(tr.loss_epoch)
             cond = np.sum((le[-1 - n:-1] / le[-2 - n:-2] - 1) > -0.0075)
@@ -406,3 +457,8 @@ def run_training_hhfm(tr):
         if args.Result == 0 and epoch % 10 == 0:
             _report(tr, "%s Epoch %d" % (tr.method, epoch), t2 - t1, t2, _evaluate(tr))
     return tr.loss_epoch
+
+
+def run_training_cars2(tr):
+    """CARS2.py:222-279: NG = 1, the plateau rule from epoch 11 (capped at 100)."""
+    return run_training_hhfm(tr, NG=1, plateau_after=10, fields=_cars2_fields)

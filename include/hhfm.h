@@ -1,7 +1,7 @@
 /*
  * hhfm.h — C ABI of the MI355X (gfx950) factorization-machine scoring backend.
  *
- * The reference (data-man-34/HHFM, Newcode/{FM,OurModel7,AFM,DFM}.py) has no native code and no FFI:
+ * The reference (data-man-34/HHFM, Newcode/{FM,OurModel7,AFM,DFM,CARS2}.py) has no native code and no FFI:
  * its hot path is a chain of TensorFlow-1.x graph ops run through
  * `model.sess.run(...)`.  Each entry point below replaces one such op chain
  * (reference file:line cited per function).  The Python host package
@@ -951,6 +951,105 @@ int hhfm_dfm_train_step_head_det(const int32_t* idx, const float* y, int64_t B, 
                                  float lambda_l2, int32_t optimizer, float* const* acc,
                                  void* workspace, size_t ws_bytes, void* scratch,
                                  size_t scratch_bytes, float* loss, void* stream, int32_t head);
+
+/* ------------------------------------------------------------------------
+ * CARS2 — the context-aware baseline the reference's driver runs beside the
+ * four FM-family models (Newcode/CARS2.py; main.py:63).  Pure additions:
+ * HHFM_ABI_VERSION stays 6.
+ *
+ * Sizes (CARS2.py:53-56): D = hidden_factor, Dc = int(D/2.5), Dp = int(D/5),
+ * Dq = int(D/2.5); the entry points take them as arguments, each >= 1.
+ * Variables (:150-164), all row-major: UI [n_ui][D] (n_ui = n_user + n_item;
+ * fp32, or bf16 for scoring: upcast exactly), and always fp32 Context [Mc][Dc],
+ * W [D][Dp][Dc], Z [D][Dq][Dc], A [Dp], B [Dq].  Mc is the number of distinct
+ * context tuples (Train.__init__, :212-216); a row is (user id, item id,
+ * context id m), ids of UI rows in [0, n_ui), m in [0, Mc).
+ *
+ * The reference's graph (:85-105), u = UI[user], i = UI[item], c = Context[m]:
+ *   pik_p = Σ_c (Σ_d u_d W[d,p,c]) c_c      qjk_q = Σ_c (Σ_d i_d Z[d,q,c]) c_c
+ *   s     = u·i + Σ_p pik_p A_p + Σ_q qjk_q B_q
+ * The device arithmetic is the folded form — the same elementary products in
+ * another association, every sum an fp32 fmaf chain:
+ *   WA[d,c] = Σ_p W[d,p,c]·A[p]      ZB[d,c] = Σ_q Z[d,q,c]·B[q]      (D x Dc)
+ *   GA[m,:] = WA · Context[m]        GB[m,:] = ZB · Context[m]        (Mc x D)
+ *   row      s = u·i + u·GA[m] + i·GB[m]
+ *   catalog  h = u + GB[m], cst = u·GA[m], score[b,n] = h_b·UI[item n] + cst_b
+ *            (CARS2.topk, :171-187)
+ *
+ * hhfm_cars2_prepare writes GA | GB | WA | ZB, in that order and unpadded,
+ * into `prepared` (hhfm_cars2_prepared_bytes(Mc, D, Dc) bytes; 16-byte aligned
+ * for the fast row kernel).  It must be called again whenever Context, W, Z, A
+ * or B change; UI does not enter it.
+ *
+ * hhfm_cars2_score_rows: idx int32 [B][3] -> out [B].  A user or item id
+ * outside [0, n_ui) or a context id outside [0, Mc) reads row 0 and ORs
+ * HHFM_STATUS_BAD_ID into *status (status may be NULL).  UI rows that are a
+ * power-of-two number (<= 64) of 16-byte chunks take the chunked kernel, any
+ * other D (e.g. 20) a generic one-wave-per-row kernel.
+ *
+ * hhfm_cars2_catalog_topk: q int32 [B][2] = (user id, context id); items are
+ * rows [item_row_begin, item_row_begin + item_count) of UI.  A query kernel
+ * writes h and cst into the hhfm_catalog_topk_workspace layout, then the
+ * dense / streaming / ring / merge paths of hhfm_catalog_topk_ex run
+ * unchanged, on their HHFM_MODE_FM form with w = NULL.  Workspace
+ * (hhfm_catalog_topk_workspace(B, item_count, D, K)), plan flags, shape limits
+ * (D/8 fp32 or D/16 bf16 a power of two <= 16, K <= 64, K <= item_count), the
+ * (score desc, index asc) order and the error codes are that entry point's.
+ * The small-catalog fused kernel is never taken.  Bad ids as above.
+ *
+ * hhfm_cars2_train_step (partial_fit, :87, :103-136, :167-170): X int32 [B][2]
+ * (user, item), Fea int32 [B] context ids, Neg int32 [B][NG], 1 <= NG <= 16.
+ *   n_b = Σ_j UI[Neg[b,j]]  (a SUM; the reference trains with NG = 1)
+ *   δ = i − n,  x_b = u·δ + δ·GB[m]   (pik·A is in both feedbacks and cancels)
+ *   loss = −Σ_b logf σ(x_b)  (+ λ·Σ var²/2 over all six variables when λ > 0)
+ * With g_b = σ(x_b) − 1:
+ *   dUI[user] += g·δ;  dUI[item] += g·(u + GB[m]);  dUI[Neg[b,j]] −= g·(u + GB[m])
+ *   for every j (a repeated id receives every contribution);
+ *   dContext[m][c] += g·Σ_d δ_d ZB[d,c];   T[d,c] = Σ_b g_b δ_bd c_bc;
+ *   dZ[d,q,c] = B_q·T[d,c];   dB[q] = Σ_{d,c} Z[d,q,c]·T[d,c];
+ *   W and A: the data gradient is identically zero, only λ acts on them.
+ * Optimizer rules as in H6 (enum hhfm_optimizer).  λ > 0: every variable is
+ * dense.  λ <= 0 is λ = 0 (:115): UI and Context follow the IndexedSlices
+ * rules, Z and B are dense, W and A receive a dense zero gradient.  acc: 6
+ * slot arrays in the order UI, Context, W, Z, A, B (ignored under SGD).
+ * *loss is the loss of the pre-update parameters.  Float atomics: not
+ * deterministic.  fp32 only.  B = 0 is a step like any other.
+ * Workspace: hhfm_cars2_train_workspace(B, ...) bytes for batches of at most B
+ * rows, zero-filled once; its first hhfm_cars2_train_state_bytes bytes are the
+ * persistent part (gradient buffers, Adam's β powers, the touched masks), left
+ * zeroed but for the powers; the rest is per-batch scratch, so a workspace
+ * grown for a larger batch keeps its state by copying that prefix.
+ * Checks, in order: sizes (HHFM_EINVAL), NG > 16 or D > 512
+ * (HHFM_EUNSUPPORTED), the optimizer code (HHFM_EUNSUPPORTED), NULL variables /
+ * loss / workspace, NULL rows at B > 0, NULL slots (HHFM_EINVAL), a short
+ * workspace (HHFM_EWORKSPACE) — all before anything is launched.
+ * Not built: a deterministic CARS2 step, bf16 training tables, a CARS2 form of
+ * the small-catalog fused kernel.
+ * (numpy restatement in the reference's op order: tests/cars2_ref.py.)
+ * ---------------------------------------------------------------------- */
+int hhfm_cars2_prepared_bytes(int64_t Mc, int32_t D, int32_t Dc, size_t* bytes);
+int hhfm_cars2_prepare(const float* Context, int64_t Mc, const float* W, const float* A,
+                       const float* Z, const float* B, int32_t D, int32_t Dc, int32_t Dp,
+                       int32_t Dq, void* prepared, size_t prepared_bytes, void* stream);
+int hhfm_cars2_score_rows(const int32_t* idx, int64_t B, const void* UI, int64_t n_ui,
+                          int32_t D, int32_t dtype, const void* prepared, int64_t Mc,
+                          float* out, int32_t* status, void* stream);
+int hhfm_cars2_catalog_topk(const int32_t* q, int64_t B, const void* UI, int64_t n_ui,
+                            int32_t D, int32_t dtype, const void* prepared, int64_t Mc,
+                            int32_t item_row_begin, int32_t item_count,
+                            int32_t global_item_base, int32_t K, float* top_score,
+                            int32_t* top_idx, void* workspace, size_t ws_bytes, int32_t plan,
+                            int32_t* status, void* stream);
+int hhfm_cars2_train_workspace(int64_t B, int64_t n_ui, int64_t Mc, int32_t D, int32_t Dc,
+                               int32_t Dp, int32_t Dq, size_t* ws_bytes);
+int hhfm_cars2_train_state_bytes(int64_t n_ui, int64_t Mc, int32_t D, int32_t Dc, int32_t Dp,
+                                 int32_t Dq, size_t* state_bytes);
+int hhfm_cars2_train_step(const int32_t* X, const int32_t* Fea, const int32_t* Neg, int64_t B,
+                          int32_t NG, float* UI, int64_t n_ui, float* Context, int64_t Mc,
+                          float* W, float* Z, float* A, float* Bv, int32_t D, int32_t Dc,
+                          int32_t Dp, int32_t Dq, float lr, float lambda_l2, int32_t optimizer,
+                          float* const* acc, void* workspace, size_t ws_bytes, float* loss,
+                          void* stream);
 
 /* tf.nn.top_k(scores, K) over a materialised score matrix [B][ld] (first N
  * columns), K <= 64; ids reported as global_item_base + column. */

@@ -219,8 +219,6 @@ void cars2_launch_queries(const int32_t* q, int64_t B, int64_t Bpad, const char*
 // ---------------------------------------------------------------------------
 // training (include/hhfm.h "CARS2": loss, gradients)
 // ---------------------------------------------------------------------------
-constexpr int kCars2MaxNeg = 16;   // train.hip's kMaxNeg
-
 // One wave per batch row:
 //   n = Σ_j UI[Neg_j], δ = i − n, x = u·δ + δ·GB[m], g = σ(x) − 1
 //   dUI[user] += g·δ; dUI[item] += g·(u + GB[m]); dUI[Neg_j] −= g·(u + GB[m])
@@ -241,14 +239,14 @@ __global__ __launch_bounds__(256) void cars2_train_rows(
     const int64_t iu = clamp_id(X[b * 2], n_ui), ii = clamp_id(X[b * 2 + 1], n_ui);
     const int64_t im = clamp_id(Fea[b], Mc);
     const int32_t* ng = Neg + b * NG;
-    int32_t nid[kCars2MaxNeg];
+    int32_t nid[kMaxNeg];
 #pragma unroll
-    for (int j = 0; j < kCars2MaxNeg; ++j) nid[j] = j < NG ? clamp_id(ng[j], n_ui) : 0;
+    for (int j = 0; j < kMaxNeg; ++j) nid[j] = j < NG ? clamp_id(ng[j], n_ui) : 0;
     float x = 0.f;
     for (int e = l; e < D; e += kWave) {
       float n = 0.f;
 #pragma unroll
-      for (int j = 0; j < kCars2MaxNeg; ++j)
+      for (int j = 0; j < kMaxNeg; ++j)
         if (j < NG) n += UI[(int64_t)nid[j] * D + e];      // Negitems: a sum   :87
       const float dl = UI[ii * D + e] - n;
       sd[e] = dl;
@@ -265,7 +263,7 @@ __global__ __launch_bounds__(256) void cars2_train_rows(
       atomicAdd(dUI + iu * D + e, g * dl);
       atomicAdd(dUI + ii * D + e, g * hv);
 #pragma unroll
-      for (int j = 0; j < kCars2MaxNeg; ++j)
+      for (int j = 0; j < kMaxNeg; ++j)
         if (j < NG) atomicAdd(dUI + (int64_t)nid[j] * D + e, -g * hv);
     }
     __builtin_amdgcn_wave_barrier();   // the wave's LDS accesses are in order

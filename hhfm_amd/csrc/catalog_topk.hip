@@ -23,9 +23,10 @@
 // Order everywhere: score descending, item index ascending (tf.nn.top_k).
 #include "cars2.h"
 #include "gemm_mfma.h"
-#include "hhfm_pool.h"
+#include "hhfm_feature.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace hhfm {
 
@@ -78,11 +79,15 @@ constexpr int kTile = 32;  // items per MFMA tile
 // ---------------------------------------------------------------------------
 // 1. query vectors
 // ---------------------------------------------------------------------------
-template <bool BF16>
+// One walk over the feature policy (hhfm_feature.h), so h is the row kernels'
+// h bit for bit; each instantiation is a kernel of its own and keeps its code
+// and registers.  HHFM_MODE_FM (q = u + f, cst = q·f) exists in the SumFeature
+// instantiation alone; the pooled and the two-way one are HHFM_MODE_HHFM, cst 0.
+template <bool BF16, class Feature>
 __global__ __launch_bounds__(256) void catalog_queries(
     const int32_t* __restrict__ qidx, int64_t B, int64_t Bpad, int ncols,
     int mode, int ucol, int c0, int c1, int t0, int t1,
-    const char* __restrict__ E, int64_t M, int k, float* __restrict__ H,
+    const char* __restrict__ E, int64_t M, int k, Feature feat, float* __restrict__ H,
     float* __restrict__ cst) {
   const int lane = lane_id();
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
@@ -93,98 +98,32 @@ __global__ __launch_bounds__(256) void catalog_queries(
     return BF16 ? bf16_to_f32(reinterpret_cast<const uint16_t*>(r)[e])
                 : reinterpret_cast<const float*>(r)[e];
   };
+  constexpr bool kHasFm = std::is_same_v<Feature, SumFeature>;
   for (int64_t b = wave; b < Bpad; b += nwave) {
     float part = 0.f;
     if (b < B) {
       const int32_t* p = qidx + b * (int64_t)ncols;
       for (int e = lane; e < k; e += kWave) {
         const float u = val(p[ucol], e);
-        float ctx = 0.f, tim = 0.f;
-        for (int c = c0; c < c1; ++c) ctx += val(p[c], e);
-        for (int c = t0; c < t1; ++c) tim += val(p[c], e);
-        float h;
-        if (mode == HHFM_MODE_FM) {
-          h = u + ctx;          // UserWithFeature            FM.py:177
-          part += h * ctx;      // item-independent (u+f)·f   FM.py:178-183
-        } else {
-          h = u;                // Σ[user, Σctx, Σtime]        OurModel7.py:270-292
-          if (c1 > c0) h = h + ctx;
-          if (t1 > t0) h = h + tim;
+        auto row = [&](int c) { return val(p[c], e); };
+        if constexpr (kHasFm) {
+          if (mode == HHFM_MODE_FM) {
+            float ctx = 0.f;
+            for (int c = c0; c < c1; ++c) ctx += row(c);
+            const float h = u + ctx;   // UserWithFeature            FM.py:177
+            part += h * ctx;           // item-independent (u+f)·f   FM.py:178-183
+            H[b * k + e] = h;
+            continue;
+          }
         }
-        H[b * k + e] = h;
+        // Σ[user, Σctx, Σtime] (OurModel7.py:270-292), or its pools
+        H[b * k + e] = feat.forward(u, row, c0, c1, t0, t1).h;
       }
     } else {
       for (int e = lane; e < k; e += kWave) H[b * k + e] = 0.f;
     }
-    part = group_sum<kWave>(part);
+    if constexpr (kHasFm) part = group_sum<kWave>(part);
     if (lane == 0) cst[b] = part;
-  }
-}
-
-// HHFM_MODE_HHFM with MAX / MEAN pooling (include/hhfm.h "Pooling"): the same
-// walk with h from hhfm_pool.h — the row kernels' h bit for bit; cst stays 0.
-// A kernel of its own, so that catalog_queries keeps its code and registers.
-template <bool BF16>
-__global__ __launch_bounds__(256) void catalog_queries_pool(
-    const int32_t* __restrict__ qidx, int64_t B, int64_t Bpad, int ncols,
-    int ucol, int c0, int c1, int t0, int t1, const char* __restrict__ E, int64_t M,
-    int k, PoolModes pm, float* __restrict__ H, float* __restrict__ cst) {
-  const int lane = lane_id();
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
-  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
-  const int esz = BF16 ? 2 : 4;
-  auto val = [&](int32_t id, int e) -> float {
-    const char* r = E + (int64_t)clamp_id(id, M) * k * esz;
-    return BF16 ? bf16_to_f32(reinterpret_cast<const uint16_t*>(r)[e])
-                : reinterpret_cast<const float*>(r)[e];
-  };
-  for (int64_t b = wave; b < Bpad; b += nwave) {
-    if (b < B) {
-      const int32_t* p = qidx + b * (int64_t)ncols;
-      for (int e = lane; e < k; e += kWave) {
-        float cv = pool_identity(pm.ctx), tv = pool_identity(pm.tim);
-        for (int c = c0; c < c1; ++c) cv = pool_step(pm.ctx, cv, val(p[c], e));
-        for (int c = t0; c < t1; ++c) tv = pool_step(pm.tim, tv, val(p[c], e));
-        cv = pool_finish(pm.ctx, cv, c1 - c0);
-        tv = pool_finish(pm.tim, tv, t1 - t0);
-        H[b * k + e] = pool_h(val(p[ucol], e), cv, c1 - c0, tv, t1 - t0, pm.fin);
-      }
-    } else {
-      for (int e = lane; e < k; e += kWave) H[b * k + e] = 0.f;
-    }
-    if (lane == 0) cst[b] = 0.f;
-  }
-}
-
-// HHFM_MODE_HHFM, two-way (include/hhfm.h "Two-way pooling"): the same walk
-// with h from two_way_h of hhfm_pool.h — the two-way row kernels' h bit for
-// bit; cst stays 0.  A kernel of its own, so that catalog_queries and
-// catalog_queries_pool keep their code and registers.
-template <bool BF16>
-__global__ __launch_bounds__(256) void catalog_queries_two_way(
-    const int32_t* __restrict__ qidx, int64_t B, int64_t Bpad, int ncols,
-    int ucol, int c0, int c1, int t0, int t1, const char* __restrict__ E, int64_t M,
-    int k, PoolModes2 pm, float* __restrict__ H, float* __restrict__ cst) {
-  const int lane = lane_id();
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
-  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
-  const int esz = BF16 ? 2 : 4;
-  auto val = [&](int32_t id, int e) -> float {
-    const char* r = E + (int64_t)clamp_id(id, M) * k * esz;
-    return BF16 ? bf16_to_f32(reinterpret_cast<const uint16_t*>(r)[e])
-                : reinterpret_cast<const float*>(r)[e];
-  };
-  for (int64_t b = wave; b < Bpad; b += nwave) {
-    if (b < B) {
-      const int32_t* p = qidx + b * (int64_t)ncols;
-      for (int e = lane; e < k; e += kWave)
-        H[b * k + e] = two_way_h(
-            val(p[ucol], e), [&](int i) { return val(p[c0 + i], e); }, c1 - c0,
-            [&](int i) { return val(p[t0 + i], e); }, t1 - t0, pm).h;
-    } else {
-      for (int e = lane; e < k; e += kWave) H[b * k + e] = 0.f;
-    }
-    if (lane == 0) cst[b] = 0.f;
   }
 }
 
@@ -1470,7 +1409,7 @@ extern "C" int hhfm_catalog_topk(
 }
 
 // hhfm_catalog_topk_ex (pooling 0) and hhfm_catalog_topk_pool: a pooled call
-// differs in how h is formed alone — catalog_queries_pool, or the POOL form of
+// differs in how h is formed alone — catalog_queries over PoolFeature, or the POOL form of
 // the fused small-catalog kernel's step 0.
 static int catalog_topk_impl(
     const int32_t* qidx, int64_t B, int32_t ncols, int32_t mode,
@@ -1532,7 +1471,7 @@ static int catalog_topk_impl(
   // its 32 queries); HHFM_PLAN_STORE forces the score-matrix path,
   // HHFM_PLAN_FUSED the fused kernel up to the dense limit
   // (two-way has no form of the fused kernel: it always forms H with
-  // catalog_queries_two_way and runs the main kernels below)
+  // catalog_queries over TwoWayFeature and runs the main kernels below)
   const bool fused_size = item_count <= 8192 || (plan & HHFM_PLAN_FUSED);
   if (!two_way && !cars2 && p.dense && fused_size && K <= 32 && KT <= 8 && p.fS <= kFusedMaxS &&
       (B + kQPerWave - 1) / kQPerWave <= kFusedMaxGroups &&
@@ -1560,32 +1499,21 @@ static int catalog_topk_impl(
   {
     int64_t blocks = (p.Bpad + 3) / 4;
     if (blocks > 4096) blocks = 4096;
+    auto queries = [&](auto feat) {
+      using Feature = decltype(feat);
+      auto kernel = bf16 ? catalog_queries<true, Feature> : catalog_queries<false, Feature>;
+      hipLaunchKernelGGL(kernel, dim3((int)blocks), dim3(256), 0, st, qidx, B, p.Bpad, ncols, mode,
+                         user_col, ctx_begin, ctx_end, time_begin, time_end, Eb, features_M, k,
+                         feat, H, cst);
+    };
     if (cars2)   // CARS2: h = u + GB[m], cst = u·GA[m]; the main kernels' FM form with w = NULL
       cars2_launch_queries(qidx, B, p.Bpad, Eb, bf16, features_M, k, *cars2, H, cst, status, st);
-    else if (two_way && bf16)
-      hipLaunchKernelGGL(catalog_queries_two_way<true>, dim3((int)blocks), dim3(256), 0, st,
-                         qidx, B, p.Bpad, ncols, user_col, ctx_begin, ctx_end, time_begin,
-                         time_end, Eb, features_M, k, pm2, H, cst);
     else if (two_way)
-      hipLaunchKernelGGL(catalog_queries_two_way<false>, dim3((int)blocks), dim3(256), 0, st,
-                         qidx, B, p.Bpad, ncols, user_col, ctx_begin, ctx_end, time_begin,
-                         time_end, Eb, features_M, k, pm2, H, cst);
-    else if (pooling != 0 && bf16)
-      hipLaunchKernelGGL(catalog_queries_pool<true>, dim3((int)blocks), dim3(256), 0, st,
-                         qidx, B, p.Bpad, ncols, user_col, ctx_begin, ctx_end, time_begin,
-                         time_end, Eb, features_M, k, pm, H, cst);
+      queries(TwoWayFeature{pm2});
     else if (pooling != 0)
-      hipLaunchKernelGGL(catalog_queries_pool<false>, dim3((int)blocks), dim3(256), 0, st,
-                         qidx, B, p.Bpad, ncols, user_col, ctx_begin, ctx_end, time_begin,
-                         time_end, Eb, features_M, k, pm, H, cst);
-    else if (bf16)
-      hipLaunchKernelGGL(catalog_queries<true>, dim3((int)blocks), dim3(256), 0, st,
-                         qidx, B, p.Bpad, ncols, mode, user_col, ctx_begin,
-                         ctx_end, time_begin, time_end, Eb, features_M, k, H, cst);
+      queries(PoolFeature{pm});
     else
-      hipLaunchKernelGGL(catalog_queries<false>, dim3((int)blocks), dim3(256), 0, st,
-                         qidx, B, p.Bpad, ncols, mode, user_col, ctx_begin,
-                         ctx_end, time_begin, time_end, Eb, features_M, k, H, cst);
+      queries(SumFeature{});
   }
 
   if (p.dense) {
@@ -1722,7 +1650,7 @@ extern "C" int hhfm_catalog_topk_pool(
                            pooling, status, stream);
 }
 
-// Two-way: H from catalog_queries_two_way, then the main kernels unchanged;
+// Two-way: H from catalog_queries over TwoWayFeature, then the main kernels unchanged;
 // never the small-catalog fused kernel (a two-way form of catalog_fused.h is
 // not built).
 extern "C" int hhfm_catalog_topk_pool2(

@@ -17,7 +17,7 @@
 //     the xor-32/16 steps of LPR 64 / 32 go through ds_bpermute_b32 (LDS
 //     hardware, no LDS allocation).  No atomics, one fp32 store per row.
 #include "hhfm_common.h"
-#include "hhfm_pool.h"
+#include "hhfm_feature.h"
 
 namespace hhfm {
 
@@ -605,11 +605,13 @@ __global__ __launch_bounds__(256) void hybrid_rows_fast(
   report_bad_id(status, bad);
 }
 
-template <bool BF16>
+// any layout, any k, with h from the feature policy (hhfm_feature.h: the sum,
+// the pooled or the two-way h); each instantiation is a kernel of its own
+template <bool BF16, class Feature>
 __global__ __launch_bounds__(256) void hybrid_rows_generic(
     const int32_t* __restrict__ idx, int64_t B, int ncols, int ucol, int icol,
     int c0, int c1, int t0, int t1, const char* __restrict__ E, int64_t M,
-    int k, float* __restrict__ out, int32_t* __restrict__ status) {
+    int k, float* __restrict__ out, Feature feat, int32_t* __restrict__ status) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
   const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
@@ -628,20 +630,9 @@ __global__ __launch_bounds__(256) void hybrid_rows_generic(
       if (c == ucol || c == icol || (c >= c0 && c < c1) || (c >= t0 && c < t1))
         bad |= clamp_id(p[c], M) != p[c];
     float t = 0.f;
-    for (int e = lane; e < k; e += kWave) {
-      float h = val(p[ucol], e);
-      if (c1 > c0) {
-        float s = 0.f;
-        for (int c = c0; c < c1; ++c) s += val(p[c], e);
-        h = h + s;
-      }
-      if (t1 > t0) {
-        float s = 0.f;
-        for (int c = t0; c < t1; ++c) s += val(p[c], e);
-        h = h + s;
-      }
-      t += h * val(p[icol], e);
-    }
+    for (int e = lane; e < k; e += kWave)
+      t += feat.forward(val(p[ucol], e), [&](int c) { return val(p[c], e); }, c0, c1, t0, t1).h *
+           val(p[icol], e);
     t = group_sum<kWave>(t);
     if (lane == 0) out[row] = t;
   }
@@ -765,42 +756,6 @@ __global__ __launch_bounds__(256) void hybrid_rows_pool(
       const int64_t row = base + (int64_t)u * RPW + g;
       if (sub == 0 && row < B) out[row] = t;
     }
-  }
-  report_bad_id(status, bad);
-}
-
-// any layout, any k: hybrid_rows_generic with the pooled h
-template <bool BF16>
-__global__ __launch_bounds__(256) void hybrid_rows_generic_pool(
-    const int32_t* __restrict__ idx, int64_t B, int ncols, int ucol, int icol,
-    int c0, int c1, int t0, int t1, const char* __restrict__ E, int64_t M,
-    int k, float* __restrict__ out, PoolModes pm, int32_t* __restrict__ status) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
-  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
-  const int esz = BF16 ? 2 : 4;
-  auto val = [&](int32_t id, int e) -> float {
-    const char* r = E + (int64_t)clamp_id(id, M) * k * esz;
-    return BF16 ? bf16_to_f32(reinterpret_cast<const uint16_t*>(r)[e])
-                : reinterpret_cast<const float*>(r)[e];
-  };
-  bool bad = false;
-  for (int64_t row = wave; row < B; row += nwave) {
-    const int32_t* p = idx + row * (int64_t)ncols;
-    for (int c = lane; c < ncols; c += kWave)
-      if (c == ucol || c == icol || (c >= c0 && c < c1) || (c >= t0 && c < t1))
-        bad |= clamp_id(p[c], M) != p[c];
-    float t = 0.f;
-    for (int e = lane; e < k; e += kWave) {
-      float cv = pool_identity(pm.ctx), tv = pool_identity(pm.tim);
-      for (int c = c0; c < c1; ++c) cv = pool_step(pm.ctx, cv, val(p[c], e));
-      for (int c = t0; c < t1; ++c) tv = pool_step(pm.tim, tv, val(p[c], e));
-      cv = pool_finish(pm.ctx, cv, c1 - c0);
-      tv = pool_finish(pm.tim, tv, t1 - t0);
-      t += pool_h(val(p[ucol], e), cv, c1 - c0, tv, t1 - t0, pm.fin) * val(p[icol], e);
-    }
-    t = group_sum<kWave>(t);
-    if (lane == 0) out[row] = t;
   }
   report_bad_id(status, bad);
 }
@@ -947,40 +902,6 @@ __global__ __launch_bounds__(256) void hybrid_rows_two_way(
       const int64_t row = base + (int64_t)u * RPW + g;
       if (sub == 0 && row < B) out[row] = t;
     }
-  }
-  report_bad_id(status, bad);
-}
-
-// any layout, any k: hybrid_rows_generic_pool with the two-way h
-template <bool BF16>
-__global__ __launch_bounds__(256) void hybrid_rows_generic_two_way(
-    const int32_t* __restrict__ idx, int64_t B, int ncols, int ucol, int icol,
-    int c0, int c1, int t0, int t1, const char* __restrict__ E, int64_t M,
-    int k, float* __restrict__ out, PoolModes2 pm, int32_t* __restrict__ status) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
-  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
-  const int esz = BF16 ? 2 : 4;
-  auto val = [&](int32_t id, int e) -> float {
-    const char* r = E + (int64_t)clamp_id(id, M) * k * esz;
-    return BF16 ? bf16_to_f32(reinterpret_cast<const uint16_t*>(r)[e])
-                : reinterpret_cast<const float*>(r)[e];
-  };
-  bool bad = false;
-  for (int64_t row = wave; row < B; row += nwave) {
-    const int32_t* p = idx + row * (int64_t)ncols;
-    for (int c = lane; c < ncols; c += kWave)
-      if (c == ucol || c == icol || (c >= c0 && c < c1) || (c >= t0 && c < t1))
-        bad |= clamp_id(p[c], M) != p[c];
-    float t = 0.f;
-    for (int e = lane; e < k; e += kWave) {
-      const TwoWay w = two_way_h(
-          val(p[ucol], e), [&](int i) { return val(p[c0 + i], e); }, c1 - c0,
-          [&](int i) { return val(p[t0 + i], e); }, t1 - t0, pm);
-      t += w.h * val(p[icol], e);
-    }
-    t = group_sum<kWave>(t);
-    if (lane == 0) out[row] = t;
   }
   report_bad_id(status, bad);
 }
@@ -1221,6 +1142,17 @@ static int lpr_for(int64_t k, int dtype) {
   return (int)(row_bytes / 16);
 }
 
+// the generic fall-back of the three hhfm_hybrid_score_rows* entry points
+template <class Feature>
+static void launch_hybrid_generic(Feature feat, const int32_t* idx, int64_t B, int ncols, int ucol,
+                                  int icol, int c0, int c1, int t0, int t1, const char* E,
+                                  int64_t M, int k, bool bf16, float* out, int32_t* status,
+                                  hipStream_t s) {
+  auto kernel = bf16 ? hybrid_rows_generic<true, Feature> : hybrid_rows_generic<false, Feature>;
+  hipLaunchKernelGGL(kernel, dim3(grid_for(B, 4, s)), dim3(256), 0, s, idx, B, ncols, ucol, icol,
+                     c0, c1, t0, t1, E, M, k, out, feat, status);
+}
+
 }  // namespace hhfm
 
 using namespace hhfm;
@@ -1340,19 +1272,10 @@ extern "C" int hhfm_hybrid_score_rows_ex(const int32_t* idx, int64_t B,
   if (!(canonical && lpr && aligned &&
         try_hybrid_fast(idx, B, ncols, nctx,
                         reinterpret_cast<const char*>(E), features_M, lpr,
-                        bf16, out, status, s))) {
-    const int grid = grid_for(B, 4, s);
-    if (bf16)
-      hipLaunchKernelGGL(hybrid_rows_generic<true>, dim3(grid), dim3(256), 0, s,
-                         idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
-                         time_begin, time_end,
-                         reinterpret_cast<const char*>(E), features_M, k, out, status);
-    else
-      hipLaunchKernelGGL(hybrid_rows_generic<false>, dim3(grid), dim3(256), 0,
-                         s, idx, B, ncols, user_col, item_col, ctx_begin,
-                         ctx_end, time_begin, time_end,
-                         reinterpret_cast<const char*>(E), features_M, k, out, status);
-  }
+                        bf16, out, status, s)))
+    launch_hybrid_generic(SumFeature{}, idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
+                          time_begin, time_end, reinterpret_cast<const char*>(E), features_M, k,
+                          bf16, out, status, s);
   return (int)hipGetLastError();
 }
 
@@ -1370,7 +1293,7 @@ extern "C" int hhfm_hybrid_score_rows(const int32_t* idx, int64_t B,
 
 // H1 with pooling: pooling == 0 is hhfm_hybrid_score_rows_ex itself; any other
 // legal word runs hybrid_rows_pool (same shapes as hybrid_rows_fast) or
-// hybrid_rows_generic_pool.  Argument checks as in hhfm_hybrid_score_rows_ex.
+// hybrid_rows_generic over PoolFeature.  Argument checks as in hhfm_hybrid_score_rows_ex.
 extern "C" int hhfm_hybrid_score_rows_pool(const int32_t* idx, int64_t B,
                                            int32_t ncols, int32_t user_col,
                                            int32_t item_col, int32_t ctx_begin,
@@ -1409,24 +1332,15 @@ extern "C" int hhfm_hybrid_score_rows_pool(const int32_t* idx, int64_t B,
                          2 + nctx + ntime == ncols;
   if (!(canonical && lpr && aligned &&
         try_hybrid_pool(idx, B, ncols, nctx, reinterpret_cast<const char*>(E),
-                        features_M, lpr, bf16, out, pm, status, s))) {
-    const int grid = grid_for(B, 4, s);
-    if (bf16)
-      hipLaunchKernelGGL(hybrid_rows_generic_pool<true>, dim3(grid), dim3(256), 0, s,
-                         idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
-                         time_begin, time_end, reinterpret_cast<const char*>(E),
-                         features_M, k, out, pm, status);
-    else
-      hipLaunchKernelGGL(hybrid_rows_generic_pool<false>, dim3(grid), dim3(256), 0, s,
-                         idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
-                         time_begin, time_end, reinterpret_cast<const char*>(E),
-                         features_M, k, out, pm, status);
-  }
+                        features_M, lpr, bf16, out, pm, status, s)))
+    launch_hybrid_generic(PoolFeature{pm}, idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
+                          time_begin, time_end, reinterpret_cast<const char*>(E), features_M, k,
+                          bf16, out, status, s);
   return (int)hipGetLastError();
 }
 
 // H1, two-way: hybrid_rows_two_way on the reference's canonical layouts,
-// hybrid_rows_generic_two_way everywhere else.  pooling2 == 0 is still the
+// hybrid_rows_generic over TwoWayFeature everywhere else.  pooling2 == 0 is still the
 // two-way model (no routing to the one-way kernels).
 extern "C" int hhfm_hybrid_score_rows_pool2(const int32_t* idx, int64_t B,
                                             int32_t ncols, int32_t user_col,
@@ -1467,17 +1381,9 @@ extern "C" int hhfm_hybrid_score_rows_pool2(const int32_t* idx, int64_t B,
   if (canonical && lpr && aligned)
     fast = bf16 ? try_two_way<true>(idx, B, ncols, nctx, Eb, features_M, lpr, out, pm, status, s)
                 : try_two_way<false>(idx, B, ncols, nctx, Eb, features_M, lpr, out, pm, status, s);
-  if (!fast) {
-    const int grid = grid_for(B, 4, s);
-    if (bf16)
-      hipLaunchKernelGGL(hybrid_rows_generic_two_way<true>, dim3(grid), dim3(256), 0, s,
-                         idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
-                         time_begin, time_end, Eb, features_M, k, out, pm, status);
-    else
-      hipLaunchKernelGGL(hybrid_rows_generic_two_way<false>, dim3(grid), dim3(256), 0, s,
-                         idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
-                         time_begin, time_end, Eb, features_M, k, out, pm, status);
-  }
+  if (!fast)
+    launch_hybrid_generic(TwoWayFeature{pm}, idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
+                          time_begin, time_end, Eb, features_M, k, bf16, out, status, s);
   return (int)hipGetLastError();
 }
 

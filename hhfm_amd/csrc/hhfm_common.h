@@ -13,6 +13,10 @@ namespace hhfm {
 
 constexpr int kWave = 64;  // CDNA wavefront
 
+// negatives per row of a BPR training step, kept in registers (HHFM and CARS2;
+// the reference samples 10, OurModel7.py:371)
+constexpr int kMaxNeg = 16;
+
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 

@@ -5,8 +5,9 @@
 // implementation: the row kernel (fm_rows.hip), the catalog query kernel
 // (catalog_topk.hip, catalog_fused.h) and the training forward (train.hip) all
 // form h_e through pool_step / pool_finish / pool_h, so they agree on it bit
-// for bit.  The sum-only kernels keep their own (older) expressions and are
-// not routed through here.
+// for bit.  hhfm_feature.h wraps these helpers, and the original sum's own
+// expressions (which start from +0, not from pool_identity), as the feature
+// policies the runtime-shaped kernels are instantiated over.
 #ifndef HHFM_POOL_H_
 #define HHFM_POOL_H_
 
@@ -75,9 +76,9 @@ HHFM_DEV float pool_grad(int mode, float d, float v, float mx, int n_equal, int 
 // pool of rows gains P2, the pool (by pooling2's mode) of its pair products
 // r_i · r_j, i < j, i outer, and the stack gains H2 over its member products.
 // two_way_h below is the one implementation the generic row kernel, the
-// catalog query kernel and the training forward call, so they agree on h bit
-// for bit; hybrid_rows_two_way (fm_rows.hip) unrolls the same expressions over
-// its registers.
+// catalog query kernel and the training forward call (through TwoWayFeature
+// of hhfm_feature.h), so they agree on h bit for bit; hybrid_rows_two_way
+// (fm_rows.hip) unrolls the same expressions over its registers.
 // ---------------------------------------------------------------------------
 struct PoolModes2 {
   PoolModes one, two;   // pooling (P1, H1) and pooling2 (P2, H2)

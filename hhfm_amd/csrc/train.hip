@@ -45,15 +45,14 @@
 #include <cfloat>
 #include <initializer_list>
 #include <iterator>
+#include <type_traits>
 
 #include "cars2.h"
 #include "dropout.h"
 #include "gemm_mfma.h"
-#include "hhfm_pool.h"
+#include "hhfm_feature.h"
 
 namespace hhfm {
-
-constexpr int kMaxNeg = 16;   // negatives per row (the reference samples 10, OurModel7.py:371)
 
 // The scalar block's slots.  kScalAdam: Adam's β1^t, β2^t (kept between steps)
 // and a flag that is != 0 once Adam has taken a step (a separate flag: β1^t
@@ -140,34 +139,41 @@ __global__ __launch_bounds__(256) void fm_train_rows(
   }
 }
 
-// HHFM: loss_b = -log σ(pos - max_j neg_j); h = u + Σctx (+ Σtime)
+// HHFM: loss_b = -log σ(pos - max_j neg_j) with h from the feature policy
+// (hhfm_feature.h: SumFeature h = u + Σctx (+ Σtime) or TwoWayFeature — the
+// scoring kernels' h bit for bit; the pooled step is hhfm_train_rows_pool
+// below).  The BPR part — reduce_max over the negatives with ties split, g,
+// gt, dh — is stated here for the default, the deterministic and the two-way
+// step; each instantiation is a kernel of its own and keeps its code and
+// registers.
+// DET = false: the item and negative scatters, Feature::back's per-row values
+// and the loss are float atomics into dE / scal (gb .. HV are null and unused).
+// DET = true (hhfm_hhfm_train_step_det): no atomics, dE / scal unused — per
+// row g (gb), gt = g / ties (gtb), bit j of the mask = negative j is a tied
+// maximum (maskb), h[c] and dh[c] = g·it − gt·nsum (HV [B][2k]: h, then dh)
+// and the loss −log σ(z) in double (lossb) are stored for det_scatter; back is
+// never called.
+template <class Feature, bool DET>
 __global__ __launch_bounds__(256) void hhfm_train_rows(
     const int32_t* __restrict__ X, const int32_t* __restrict__ Neg, int64_t B, int ncols,
     int c0, int c1, int t0, int t1, int NG, const float* __restrict__ E, int64_t M, int k,
-    float* __restrict__ dE, float* __restrict__ scal) {
+    Feature feat, float* __restrict__ dE, float* __restrict__ scal, float* __restrict__ gb,
+    float* __restrict__ gtb, uint32_t* __restrict__ maskb, double* __restrict__ lossb,
+    float* __restrict__ HV) {
   const int l = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
   const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
   for (int64_t b = wave; b < B; b += nwave) {
     const int32_t* x = X + b * ncols;
     const int32_t* ng = Neg + b * NG;
-    const int64_t iu = clamp_id(x[0], M), ii = clamp_id(x[1], M);
-    auto hval = [&](int c) {
-      float h = E[iu * k + c];
-      if (c1 > c0) {
-        float s = 0.f;
-        for (int j = c0; j < c1; ++j) s += E[(int64_t)clamp_id(x[j], M) * k + c];
-        h = h + s;
-      }
-      if (t1 > t0) {
-        float s = 0.f;
-        for (int j = t0; j < t1; ++j) s += E[(int64_t)clamp_id(x[j], M) * k + c];
-        h = h + s;
-      }
-      return h;
+    const int64_t iu = clamp_id(x[kUserCol], M), ii = clamp_id(x[kItemCol], M);
+    auto fwd = [&](int c) {
+      return feat.forward(
+          E[iu * k + c], [&](int j) { return E[(int64_t)clamp_id(x[j], M) * k + c]; }, c0, c1, t0,
+          t1);
     };
     float pos = 0.f;
-    for (int c = l; c < k; c += kWave) pos += hval(c) * E[ii * k + c];
+    for (int c = l; c < k; c += kWave) pos += fwd(c).h * E[ii * k + c];
     pos = group_sum<kWave>(pos);                        // PositiveFeadback  :171
     // NegativeFeadback (:172) for up to kMaxNeg negatives, kept in registers
     float negv[kMaxNeg];
@@ -178,7 +184,7 @@ __global__ __launch_bounds__(256) void hhfm_train_rows(
       if (j < NG) {
         float v = 0.f;
         const int64_t in = clamp_id(ng[j], M);
-        for (int c = l; c < k; c += kWave) v += hval(c) * E[in * k + c];
+        for (int c = l; c < k; c += kWave) v += fwd(c).h * E[in * k + c];
         v = group_sum<kWave>(v);
         negv[j] = v;
         mx = fmaxf(mx, v);
@@ -186,39 +192,62 @@ __global__ __launch_bounds__(256) void hhfm_train_rows(
     }
     // ties of the max share its gradient (reduce_max, :174)
     int nt = 0;
+    [[maybe_unused]] uint32_t tied = 0;
 #pragma unroll
-    for (int j = 0; j < kMaxNeg; ++j) nt += (j < NG && negv[j] == mx);
+    for (int j = 0; j < kMaxNeg; ++j) {
+      nt += (j < NG && negv[j] == mx);
+      if constexpr (DET) tied |= (uint32_t)(j < NG && negv[j] == mx) << j;
+    }
     const float z = pos - mx;
     const float sg = 1.f / (1.f + expf(-z));
     const float g = sg - 1.f;                           // d(-log σ(z))/dz      :178
     const float gt = g / (float)nt;
     for (int c = l; c < k; c += kWave) {
-      const float h = hval(c);
+      const auto f = fwd(c);
       const float it = E[ii * k + c];
       float nsum = 0.f;
 #pragma unroll
       for (int j = 0; j < kMaxNeg; ++j)
         if (j < NG && negv[j] == mx) nsum += E[(int64_t)clamp_id(ng[j], M) * k + c];
       const float dh = g * it - gt * nsum;
-      atomicAdd(dE + ii * k + c, g * h);
+      if constexpr (DET) {
+        HV[b * 2 * k + c] = f.h;
+        HV[b * 2 * k + k + c] = dh;
+      } else {
+        atomicAdd(dE + ii * k + c, g * f.h);
 #pragma unroll
-      for (int j = 0; j < kMaxNeg; ++j)
-        if (j < NG && negv[j] == mx) atomicAdd(dE + (int64_t)clamp_id(ng[j], M) * k + c, -gt * h);
-      atomicAdd(dE + iu * k + c, dh);
-      for (int j = c0; j < c1; ++j) atomicAdd(dE + (int64_t)clamp_id(x[j], M) * k + c, dh);
-      for (int j = t0; j < t1; ++j) atomicAdd(dE + (int64_t)clamp_id(x[j], M) * k + c, dh);
+        for (int j = 0; j < kMaxNeg; ++j)
+          if (j < NG && negv[j] == mx)
+            atomicAdd(dE + (int64_t)clamp_id(ng[j], M) * k + c, -gt * f.h);
+        feat.back(
+            f, dh, E[iu * k + c], [&](int j) { return E[(int64_t)clamp_id(x[j], M) * k + c]; }, c0,
+            c1, t0, t1,
+            [&](int j, float v) { atomicAdd(dE + (int64_t)clamp_id(x[j], M) * k + c, v); });
+      }
     }
-    if (l == 0) atomicAdd(scal + kScalDataLoss, -logf(sg));
+    if constexpr (DET) {
+      if (l == 0) {
+        gb[b] = g;
+        gtb[b] = gt;
+        maskb[b] = tied;
+        lossb[b] = (double)-logf(sg);
+      }
+    } else {
+      if (l == 0) atomicAdd(scal + kScalDataLoss, -logf(sg));
+    }
   }
 }
 
-// HHFM with MAX / MEAN pooling (include/hhfm.h "Pooling"): hhfm_train_rows
-// with the forward's h from hhfm_pool.h (the scoring kernels' h bit for bit)
-// and TF's pool gradients on the way back: dh_e reaches the stack members
-// through the final pool and the context / time rows through theirs
-// (pool_grad: max shares between the values equal to the maximum at that
-// element, mean divides by the count).  The BPR part — reduce_max over the
-// negatives with ties split, g, gt — and the loss are hhfm_train_rows's.
+// HHFM with MAX / MEAN pooling (include/hhfm.h "Pooling"): the same step with
+// PoolFeature's forward (the scoring kernels' h bit for bit) and TF's pool
+// gradients on the way back: dh_e reaches the stack members through the final
+// pool and the context / time rows through theirs (pool_grad: max shares
+// between the values equal to the maximum at that element, mean divides by
+// the count).  Kept as a kernel of its own, with its own copy of the BPR part
+// (reduce_max over the negatives with ties split, g, gt, the loss — a change
+// to hhfm_train_rows's is made here too): as an instantiation of the skeleton
+// above its (max, max, max) step measured 0.5 % slower than this kernel
+// (profiles/hybrid_feature_time.txt).
 __global__ __launch_bounds__(256) void hhfm_train_rows_pool(
     const int32_t* __restrict__ X, const int32_t* __restrict__ Neg, int64_t B, int ncols,
     int c0, int c1, int t0, int t1, int NG, const float* __restrict__ E, int64_t M, int k,
@@ -308,121 +337,6 @@ __global__ __launch_bounds__(256) void hhfm_train_rows_pool(
           atomicAdd(dE + (int64_t)clamp_id(x[j], M) * k + c,
                     pool_grad(pm.tim, dt, row(j, c), tv, eq, ntm));
       }
-    }
-    if (l == 0) atomicAdd(scal + kScalDataLoss, -logf(sg));
-  }
-}
-
-// Two-way HHFM (include/hhfm.h "Two-way pooling"): hhfm_train_rows_pool with
-// the forward's h from two_way_h of hhfm_pool.h (the scoring kernels' h bit
-// for bit).  On the way back dh_e reaches the stack members through H1
-// (pool_grad) and through every member product of H2 (a product sends d·s_n
-// to s_m and d·s_m to s_n); each mix's gradient reaches its rows through P1
-// and through every pair product of P2 the same way.  A max pool's ties are
-// found by re-forming the fp32 values with the forward's own expressions
-// (pool_mul), so the equality tests see the forward's bits.  One atomicAdd
-// per (row occurrence, column) carries that occurrence's summed contribution.
-// The BPR part — reduce_max over the negatives with ties split, g, gt — and
-// the loss are hhfm_train_rows's.
-__global__ __launch_bounds__(256) void hhfm_train_rows_two_way(
-    const int32_t* __restrict__ X, const int32_t* __restrict__ Neg, int64_t B, int ncols,
-    int c0, int c1, int t0, int t1, int NG, const float* __restrict__ E, int64_t M, int k,
-    PoolModes2 pm, float* __restrict__ dE, float* __restrict__ scal) {
-  const int l = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
-  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
-  const int nc = c1 > c0 ? c1 - c0 : 0, ntm = t1 > t0 ? t1 - t0 : 0;
-  const int members = 1 + (nc > 0) + (ntm > 0);       // 2 or 3 (two_way_shape_ok)
-  for (int64_t b = wave; b < B; b += nwave) {
-    const int32_t* x = X + b * ncols;
-    const int32_t* ng = Neg + b * NG;
-    const int64_t iu = clamp_id(x[0], M), ii = clamp_id(x[1], M);
-    auto row = [&](int j, int c) { return E[(int64_t)clamp_id(x[j], M) * k + c]; };
-    auto fwd = [&](int c) {
-      return two_way_h(
-          E[iu * k + c], [&](int i) { return row(c0 + i, c); }, nc,
-          [&](int i) { return row(t0 + i, c); }, ntm, pm);
-    };
-    float pos = 0.f;
-    for (int c = l; c < k; c += kWave) pos += fwd(c).h * E[ii * k + c];
-    pos = group_sum<kWave>(pos);                        // PositiveFeadback  :171
-    float negv[kMaxNeg];
-    float mx = -__builtin_huge_valf();
-#pragma unroll
-    for (int j = 0; j < kMaxNeg; ++j) {
-      negv[j] = -__builtin_huge_valf();
-      if (j < NG) {
-        float v = 0.f;
-        const int64_t in = clamp_id(ng[j], M);
-        for (int c = l; c < k; c += kWave) v += fwd(c).h * E[in * k + c];
-        v = group_sum<kWave>(v);
-        negv[j] = v;
-        mx = fmaxf(mx, v);
-      }
-    }
-    int nt = 0;
-#pragma unroll
-    for (int j = 0; j < kMaxNeg; ++j) nt += (j < NG && negv[j] == mx);
-    const float z = pos - mx;
-    const float sg = 1.f / (1.f + expf(-z));
-    const float g = sg - 1.f;                           // d(-log σ(z))/dz      :178
-    const float gt = g / (float)nt;
-    // the gradient of one mix (value w, gradient d) towards its n rows [j0, j0 + n)
-    auto mix_back = [&](int c, const Mix2& w, float d, int j0, int n, int m1, int m2) {
-      const int np = n * (n - 1) / 2;
-      int eq1 = 0, eq2 = 0;
-      for (int i = 0; i < n; ++i) {
-        const float ri = row(j0 + i, c);
-        eq1 += ri == w.p1;
-        for (int j = i + 1; j < n; ++j) eq2 += pool_mul(ri, row(j0 + j, c)) == w.p2;
-      }
-      for (int i = 0; i < n; ++i) {
-        const float ri = row(j0 + i, c);
-        float acc = pool_grad(m1, d, ri, w.p1, eq1, n);
-        for (int j = 0; j < n; ++j) {
-          if (j == i) continue;
-          const float rj = row(j0 + j, c);
-          acc += pool_grad(m2, d, pool_mul(ri, rj), w.p2, eq2, np) * rj;
-        }
-        atomicAdd(dE + (int64_t)clamp_id(x[j0 + i], M) * k + c, acc);
-      }
-    };
-    for (int c = l; c < k; c += kWave) {
-      const TwoWay w = fwd(c);
-      const float u = E[iu * k + c];
-      const float it = E[ii * k + c];
-      float nsum = 0.f;
-#pragma unroll
-      for (int j = 0; j < kMaxNeg; ++j)
-        if (j < NG && negv[j] == mx) nsum += E[(int64_t)clamp_id(ng[j], M) * k + c];
-      const float dh = g * it - gt * nsum;
-      atomicAdd(dE + ii * k + c, g * w.h);
-#pragma unroll
-      for (int j = 0; j < kMaxNeg; ++j)
-        if (j < NG && negv[j] == mx) atomicAdd(dE + (int64_t)clamp_id(ng[j], M) * k + c, -gt * w.h);
-      // the stack: s0 = u, then mix_c, then mix_t; h = H1 + H2 sends dh to both
-      const float sc = w.c.mix, st = w.t.mix;
-      const int feq = (u == w.h1) + (nc > 0 && sc == w.h1) + (ntm > 0 && st == w.h1);
-      float du = pool_grad(pm.one.fin, dh, u, w.h1, feq, members);
-      float dc = nc > 0 ? pool_grad(pm.one.fin, dh, sc, w.h1, feq, members) : 0.f;
-      float dt = ntm > 0 ? pool_grad(pm.one.fin, dh, st, w.h1, feq, members) : 0.f;
-      if (members == 3) {
-        const float p01 = pool_mul(u, sc), p02 = pool_mul(u, st), p12 = pool_mul(sc, st);
-        const int e2 = (p01 == w.h2) + (p02 == w.h2) + (p12 == w.h2);
-        const float g01 = pool_grad(pm.two.fin, dh, p01, w.h2, e2, 3);
-        const float g02 = pool_grad(pm.two.fin, dh, p02, w.h2, e2, 3);
-        const float g12 = pool_grad(pm.two.fin, dh, p12, w.h2, e2, 3);
-        du += g01 * sc + g02 * st;
-        dc += g01 * u + g12 * st;
-        dt += g02 * u + g12 * sc;
-      } else {                                          // one product: H2 = u · s under every mode
-        const float s = nc > 0 ? sc : st;
-        du += dh * s;
-        if (nc > 0) dc += dh * u; else dt += dh * u;
-      }
-      atomicAdd(dE + iu * k + c, du);
-      if (nc > 0) mix_back(c, w.c, dc, c0, nc, pm.one.ctx, pm.two.ctx);
-      if (ntm > 0) mix_back(c, w.t, dt, t0, ntm, pm.one.tim, pm.two.tim);
     }
     if (l == 0) atomicAdd(scal + kScalDataLoss, -logf(sg));
   }
@@ -797,83 +711,6 @@ __global__ __launch_bounds__(256) void fm_train_rows_det(
     if (l == 0) {
       gb[b] = -r;
       lossb[b] = 0.5 * ((double)r * (double)r);
-    }
-  }
-}
-
-// HHFM's row pass: hhfm_train_rows's forward, then per row g, gt = g / ties,
-// bit j of the mask = negative j is a tied maximum, h[c] and
-// dh[c] = g·it − gt·nsum ([B][2k]: h, then dh) and the loss −log σ(z).
-__global__ __launch_bounds__(256) void hhfm_train_rows_det(
-    const int32_t* __restrict__ X, const int32_t* __restrict__ Neg, int64_t B, int ncols,
-    int c0, int c1, int t0, int t1, int NG, const float* __restrict__ E, int64_t M, int k,
-    float* __restrict__ gb, float* __restrict__ gtb, uint32_t* __restrict__ maskb,
-    double* __restrict__ lossb, float* __restrict__ HV) {
-  const int l = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
-  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
-  for (int64_t b = wave; b < B; b += nwave) {
-    const int32_t* x = X + b * ncols;
-    const int32_t* ng = Neg + b * NG;
-    const int64_t iu = clamp_id(x[0], M), ii = clamp_id(x[1], M);
-    auto hval = [&](int c) {
-      float h = E[iu * k + c];
-      if (c1 > c0) {
-        float s = 0.f;
-        for (int j = c0; j < c1; ++j) s += E[(int64_t)clamp_id(x[j], M) * k + c];
-        h = h + s;
-      }
-      if (t1 > t0) {
-        float s = 0.f;
-        for (int j = t0; j < t1; ++j) s += E[(int64_t)clamp_id(x[j], M) * k + c];
-        h = h + s;
-      }
-      return h;
-    };
-    float pos = 0.f;
-    for (int c = l; c < k; c += kWave) pos += hval(c) * E[ii * k + c];
-    pos = group_sum<kWave>(pos);
-    float negv[kMaxNeg];
-    float mx = -__builtin_huge_valf();
-#pragma unroll
-    for (int j = 0; j < kMaxNeg; ++j) {
-      negv[j] = -__builtin_huge_valf();
-      if (j < NG) {
-        float v = 0.f;
-        const int64_t in = clamp_id(ng[j], M);
-        for (int c = l; c < k; c += kWave) v += hval(c) * E[in * k + c];
-        v = group_sum<kWave>(v);
-        negv[j] = v;
-        mx = fmaxf(mx, v);
-      }
-    }
-    int nt = 0;
-    uint32_t tied = 0;
-#pragma unroll
-    for (int j = 0; j < kMaxNeg; ++j) {
-      nt += (j < NG && negv[j] == mx);
-      tied |= (uint32_t)(j < NG && negv[j] == mx) << j;
-    }
-    const float z = pos - mx;
-    const float sg = 1.f / (1.f + expf(-z));
-    const float g = sg - 1.f;
-    const float gt = g / (float)nt;
-    for (int c = l; c < k; c += kWave) {
-      const float h = hval(c);
-      const float it = E[ii * k + c];
-      float nsum = 0.f;
-#pragma unroll
-      for (int j = 0; j < kMaxNeg; ++j)
-        if (j < NG && negv[j] == mx) nsum += E[(int64_t)clamp_id(ng[j], M) * k + c];
-      const float dh = g * it - gt * nsum;
-      HV[b * 2 * k + c] = h;
-      HV[b * 2 * k + k + c] = dh;
-    }
-    if (l == 0) {
-      gb[b] = g;
-      gtb[b] = gt;
-      maskb[b] = tied;
-      lossb[b] = (double)-logf(sg);
     }
   }
 }
@@ -2412,26 +2249,31 @@ static int hhfm_train_step_impl(const int32_t* X, const int32_t* Neg, int64_t B,
   float* ws = reinterpret_cast<float*>(workspace);
   float* scal = ws + p.off_scal;
   char* sc = reinterpret_cast<char*>(scratch);
+  // the row pass over the feature policy; the deterministic one stores per-row values
+  float *gb = nullptr, *gtb = nullptr, *HV = nullptr;
+  uint32_t* maskb = nullptr;
+  double* lossb = nullptr;
+  auto rows = [&](auto feat, auto is_det) {
+    hipLaunchKernelGGL((hhfm_train_rows<decltype(feat), decltype(is_det)::value>),
+                       dim3(grid_for_n(B * 64)), dim3(256), 0, st, X, Neg, B, ncols, ctx_begin,
+                       ctx_end, time_begin, time_end, NG, E, features_M, k, feat, ws + p.off_dE,
+                       scal, gb, gtb, maskb, lossb, HV);
+  };
   if (B > 0 && two_way) {
-    hipLaunchKernelGGL(hhfm_train_rows_two_way, dim3(grid_for_n(B * 64)), dim3(256), 0, st, X,
-                       Neg, B, ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E, features_M,
-                       k, pm2, ws + p.off_dE, scal);
+    rows(TwoWayFeature{pm2}, std::false_type{});
   } else if (B > 0 && pooling != 0) {
     hipLaunchKernelGGL(hhfm_train_rows_pool, dim3(grid_for_n(B * 64)), dim3(256), 0, st, X, Neg,
                        B, ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E, features_M, k,
                        pm, ws + p.off_dE, scal);
   } else if (B > 0 && !det) {
-    hipLaunchKernelGGL(hhfm_train_rows, dim3(grid_for_n(B * 64)), dim3(256), 0, st, X, Neg, B,
-                       ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E, features_M, k,
-                       ws + p.off_dE, scal);
+    rows(SumFeature{}, std::false_type{});
   } else if (B > 0) {
-    float* gb = reinterpret_cast<float*>(sc + d.g);
-    float* gtb = reinterpret_cast<float*>(sc + d.gt);
-    uint32_t* maskb = reinterpret_cast<uint32_t*>(sc + d.mask);
-    float* HV = reinterpret_cast<float*>(sc + d.rowvec);
-    hipLaunchKernelGGL(hhfm_train_rows_det, dim3(grid_for_n(B * 64)), dim3(256), 0, st, X, Neg, B,
-                       ncols, ctx_begin, ctx_end, time_begin, time_end, NG, E, features_M, k, gb,
-                       gtb, maskb, reinterpret_cast<double*>(sc + d.loss), HV);
+    gb = reinterpret_cast<float*>(sc + d.g);
+    gtb = reinterpret_cast<float*>(sc + d.gt);
+    maskb = reinterpret_cast<uint32_t*>(sc + d.mask);
+    lossb = reinterpret_cast<double*>(sc + d.loss);
+    HV = reinterpret_cast<float*>(sc + d.rowvec);
+    rows(SumFeature{}, std::true_type{});
     const OccSource src{X, Neg, ncols, NG, ctx_begin, ctx_begin + nc, time_begin, time_begin + nt};
     const int rc = det_scatter(d, sc, src, S, B, features_M, E, k, ws + p.off_dE, nullptr, nullptr,
                                scal, HhfmContrib{gb, gtb, maskb, HV, S, NG, k}, st);

@@ -1,6 +1,7 @@
 """HHFM with MAX / MEAN pooling on the GPU (include/hhfm.h "Pooling"):
-hybrid_rows_pool / hybrid_rows_generic_pool, catalog_queries_pool and
-hhfm_train_rows_pool against the numpy restatement of tests/hhfm_pool_ref.py
+hybrid_rows_pool, the PoolFeature instantiations of hybrid_rows_generic and
+catalog_queries, and hhfm_train_rows_pool against the numpy restatement of
+tests/hhfm_pool_ref.py
 (pinned on the CPU against the reference's own outputs and central
 differences: tests/test_hhfm_pool_ref.py) and against the reference's outputs
 themselves (tests/golden/hhfm_pool.npz, hhfm_pool_losses.npz).
@@ -169,6 +170,23 @@ def test_sum_pooling_through_the_new_entry_points_is_bit_identical(k, dtype):
                               (7, 10), pooling=sss)
         assert torch.equal(ca[1], cb[1]) and torch.equal(ca[0].view(torch.int32),
                                                          cb[0].view(torch.int32))
+
+
+def test_sum_pooling_in_the_generic_pooled_kernel_is_bit_identical():
+    """The all-sum word is 0 and is routed to the sum kernels, so the test above
+    never runs hybrid_rows_generic over PoolFeature.  A layout without time
+    columns with the word (sum, max, sum) does — the word is not 0, and the
+    mode of the absent time pool changes nothing: h = (u + cv) + (-0) — at a
+    width the register kernels decline (k = 72: 288-byte rows, 18 chunks).
+    cv starts from -0 and the sum kernel's s from +0: the same bits unless the
+    first context value is -0, which a normal table does not hold."""
+    from hhfm_amd import ops
+    rng = np.random.default_rng(72)
+    X, M = _rows(rng, 64, 300, 900, (7, 2, 3), 0)
+    Eg, _ = _table(rng.normal(0, 0.01, (M, 72)).astype(np.float32), "f32")
+    a = ops.hybrid_score_rows(_dev(X), Eg, 0, 1, (2, 5), (0, 0))
+    b = ops.hybrid_score_rows(_dev(X), Eg, 0, 1, (2, 5), (0, 0), pooling=("sum", "max", "sum"))
+    assert torch.equal(a.view(torch.int32), b.view(torch.int32))
 
 
 # ---------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """The two-way HHFM model on the GPU (include/hhfm.h "Two-way pooling"):
-hybrid_rows_two_way / hybrid_rows_generic_two_way, catalog_queries_two_way and
-hhfm_train_rows_two_way against the numpy restatement of
+hybrid_rows_two_way and the TwoWayFeature instantiations of hybrid_rows_generic,
+catalog_queries and hhfm_train_rows against the numpy restatement of
 tests/hhfm_two_way_ref.py (pinned on the CPU against the reference's own
 pair-product tensors and central differences: tests/test_hhfm_two_way_ref.py).
 
@@ -353,7 +353,7 @@ def _step_binding(X, Neg, E, ctx, tim, p1, p2, lr=1.0, lam=0.0, opt=1):
 
 @pytest.mark.parametrize("name", sorted(tw.TWO_WAY_CASES))
 def test_two_way_gradient_matches_float64(name):
-    """hhfm_train_rows_two_way's raw gradient, element by element: context
+    """hhfm_train_rows<TwoWayFeature>'s raw gradient, element by element: context
     only, time only, both; NG 1 .. 16; k = 4, 64, 128, 200; the planted rows of
     two_way_case (admissibility asserted in tests/test_hhfm_two_way_ref.py)."""
     X, Neg, E, ctx, tim, ties, p1, p2, _ = tw.two_way_case(name)

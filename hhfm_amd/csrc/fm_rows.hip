@@ -198,12 +198,21 @@ __global__ __launch_bounds__(256) void fm_rows_fast(
 // loads per lane in flight in the register budget of 3 waves per SIMD, where
 // fm_rows_fast<5> holds F x U = 25 at 2 waves.
 //
-// Any input is served: the first wave-iteration with an id outside the window
-// (a clamped bad id included, unless the whole table is in the window) sends
-// its wave to the general loop below — every field from global memory, UG row
-// slots — for that iteration and the rest of its rows.  Same per-element
-// order, same lane-to-field assignment of `w`, same (t + fb) + w0 as
-// fm_rows_fast: the same bits on either path.
+// The LDS-tail loop runs full wave-iterations only (`base + RPI <= B`, scalar
+// work on the wave-uniform `base`) and asks one thing of an iteration's raw
+// ids before any row load or LDS read: every user / item id is in [0, M) and
+// every field-2.. id lies in the window — two unsigned maxima and two
+// compares (HHFM_K1_LEAN_FRONT).  It clamps nothing, raises no `bad` and masks
+// no row by `row < B`: on a hit every id is its own clamp and every row exists.
+//
+// Any input is served: the first wave-iteration that fails the verdict — an
+// id outside the window, a bad id anywhere in it — or is a wave's partial last
+// one sends its wave to the general loop below — every field from global
+// memory, UG row slots, ids clamped, `bad` raised, rows masked — for that
+// iteration and the rest of its rows.  Results and the status word do not
+// depend on which loop ran; only the speed of such iterations does.  Same
+// per-element order, same lane-to-field assignment of `w`, same (t + fb) + w0
+// as fm_rows_fast: the same bits on either path.
 // ---------------------------------------------------------------------------
 #ifndef HHFM_K1_HOT_U
 #define HHFM_K1_HOT_U 6   // row slots per lane of the LDS-tail loop
@@ -224,6 +233,20 @@ __global__ __launch_bounds__(256) void fm_rows_fast(
 //      configs[1] (profiles/k1_w_scalar_ab.txt).
 #ifndef HHFM_K1_W_SCALAR
 #define HHFM_K1_W_SCALAR 1
+#endif
+// The LDS-tail loop's front end (profiles/k1_lean_loop_ab.txt):
+//   0  every id clamped and compared per lane, `row < B` per slot;
+//   1  validity only: the loop takes full wave-iterations (a wave-uniform,
+//      scalar test) and forms one verdict per iteration from the raw ids; the
+//      general loop does the clamping, the status word and the partial
+//      iteration, so nothing of that is left in this loop.
+#ifndef HHFM_K1_LEAN_FRONT
+#define HHFM_K1_LEAN_FRONT 1
+#endif
+// fm_chunk_term on two-element vectors (v_pk_mul / v_pk_add / v_pk_fma_f32):
+// the same operations per element in the same order, the same bits
+#ifndef HHFM_K1_PK_MATH
+#define HHFM_K1_PK_MATH 1
 #endif
 constexpr int kHotWindowBytes = 16384;
 // scalar `w` loads of a wave-iteration at most (more: the vector load), and
@@ -257,20 +280,47 @@ HHFM_DEV void load_ids_slots(int32_t (&id)[UG][F], const int32_t* __restrict__ i
   }
 }
 
-// Σ_e ½((Σ_f c_f)² − Σ_f c_f²) of one lane's chunk, fields in index order
-template <int F, typename C>
+// Σ_e ½((Σ_f c_f)² − Σ_f c_f²) of one lane's chunk, fields in index order.
+// Per element, what the compiler contracts the plain expression to (here and
+// in fm_rows_fast): q = fma(v0, v0, v1·v1) — of the first two squares it is
+// the second that is rounded on its own — then q = fma(v_f, v_f, q), s += v_f,
+// x = fma(s, s, −q), t += ½·x (exact, so fused or not is the same).  PK: the
+// same steps written out on the elements (e, e + 1) together, for the packed
+// fp32 instructions; t stays one chain over e, so the bits are the same.
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+template <int F, typename C, bool PK = HHFM_K1_PK_MATH == 1>
 HHFM_DEV float fm_chunk_term(const C (&c)[F]) {
+  static_assert(F >= 2, "the first two fields open the sums");
   float t = 0.f;
+  if constexpr (PK) {
 #pragma unroll
-  for (int e = 0; e < C::kElems; ++e) {
-    float s = c[0].v[e];
-    float q = c[0].v[e] * c[0].v[e];
+    for (int e = 0; e < C::kElems; e += 2) {
+      const f32x2_t v0 = {c[0].v[e], c[0].v[e + 1]};
+      const f32x2_t v1 = {c[1].v[e], c[1].v[e + 1]};
+      f32x2_t s = v0 + v1;
+      f32x2_t q = __builtin_elementwise_fma(v0, v0, v1 * v1);
 #pragma unroll
-    for (int f = 1; f < F; ++f) {
-      s += c[f].v[e];
-      q += c[f].v[e] * c[f].v[e];
+      for (int f = 2; f < F; ++f) {
+        const f32x2_t v = {c[f].v[e], c[f].v[e + 1]};
+        s += v;
+        q = __builtin_elementwise_fma(v, v, q);
+      }
+      const f32x2_t x = __builtin_elementwise_fma(s, s, -q);
+      t = __builtin_fmaf(0.5f, x[0], t);
+      t = __builtin_fmaf(0.5f, x[1], t);
     }
-    t += 0.5f * (s * s - q);
+  } else {
+#pragma unroll
+    for (int e = 0; e < C::kElems; ++e) {
+      float s = c[0].v[e];
+      float q = c[0].v[e] * c[0].v[e];
+#pragma unroll
+      for (int f = 1; f < F; ++f) {
+        s += c[f].v[e];
+        q += c[f].v[e] * c[f].v[e];
+      }
+      t += 0.5f * (s * s - q);
+    }
   }
   return t;
 }
@@ -296,6 +346,18 @@ __global__ __launch_bounds__(256) void fm_rows_fast_hot(
   // 1.5 % slower (profiles/k1_w_scalar_ab.txt): those keep the vector load.
   constexpr bool WS = HAS_W && HHFM_K1_W_SCALAR == 1 && !BF16 && F <= 5 &&
                       2 * U * RPW <= kHotWScalarMax;
+  // Where the lean front end or the packed math would cost the kernel a wave
+  // per SIMD by registers, or take it past the 168 VGPRs of 3 waves, it keeps
+  // the earlier form (profiles/k1_lean_loop_resources.txt): the front end at
+  // F = 3 with LPR <= 8 and at fp32 F = 7 without `w`; the chunk math without
+  // `w` at bf16 F = 3, 8 and at fp32 F = 7.  bf16 tables at LPR <= 8 keep both
+  // earlier forms: F = 5 k = 64 bf16 ran 1.1 % slower with the two
+  // (profiles/k1_lean_loop_ab.txt).
+  constexpr bool NARROW_BF16 = BF16 && LPR <= 8;
+  constexpr bool LEAN = HHFM_K1_LEAN_FRONT == 1 && !NARROW_BF16 && !(F == 3 && LPR <= 8) &&
+                        !(F == 7 && !BF16 && !HAS_W);
+  constexpr bool PK = HHFM_K1_PK_MATH == 1 && !NARROW_BF16 &&
+                      !(!HAS_W && (BF16 ? (F == 3 || F == 8) : F == 7));
   static_assert(T <= 256, "local index is 8 bits");
   using C = Chunk<BF16>;
   const uint32_t M32 = id_limit32(M);
@@ -317,12 +379,17 @@ __global__ __launch_bounds__(256) void fm_rows_fast_hot(
   const bool reach = ws <= 0x7fffffff;
   const int32_t ws32 = reach ? (int32_t)ws : 0;
   const uint32_t nhit = reach ? (uint32_t)nwin : 0u;
-  const uint32_t nm1 = (uint32_t)nwin - 1u;
+  [[maybe_unused]] const uint32_t nm1 = (uint32_t)nwin - 1u;
 
   const int lane = threadIdx.x & (kWave - 1);
   const int sub = lane & (LPR - 1);
   const int g = lane / LPR;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  // LEAN: the wave's number as a scalar, so that `base` and the loop's test
+  // `base + RPI <= B` are scalar work
+  const int64_t wave =
+      LEAN ? (int64_t)blockIdx.x * (blockDim.x / kWave) +
+                 __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave))
+           : ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
   const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
   const int64_t stride = nwave * RPI;
 
@@ -332,31 +399,59 @@ __global__ __launch_bounds__(256) void fm_rows_fast_hot(
     int32_t raw[U][F];
     if (base < B) load_ids<F, U, false>(raw, idx, base, B, g, RPW, F);
 
-    for (; base < B; base += stride) {
+    // LEAN: full wave-iterations only; the partial last one of a wave is the
+    // general loop's
+    for (; LEAN ? base + RPI <= B : base < B; base += stride) {
       int32_t id01[U][2];
       uint32_t pk[U][PKW];
       bool miss = false;
+      if constexpr (LEAN) {
+        // one verdict from the raw ids: every user / item id is in [0, M)
+        // (unsigned maximum < M32) and every field-2.. id is in the window
+        // (maximum of the local indices < nhit).  Nothing is clamped: on a
+        // miss nothing below runs, and on a hit every id is its own clamp.
+        uint32_t hi = 0u, dm = 0u;
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
+        for (int u = 0; u < U; ++u) {
 #pragma unroll
-        for (int j = 0; j < PKW; ++j) pk[u][j] = 0u;
-        bool m = false;
+          for (int j = 0; j < PKW; ++j) pk[u][j] = 0u;
 #pragma unroll
-        for (int f = 0; f < F; ++f) {
-          const int32_t id = clamp_id32(raw[u][f], M32);
-          bad |= id != raw[u][f];
-          if (f < 2) {
-            id01[u][f] = id;
-          } else {
-            const uint32_t d = (uint32_t)(id - ws32);
-            m |= d >= nhit;
-            pk[u][(f - 2) >> 2] |= (d < nm1 ? d : nm1) << (8 * ((f - 2) & 3));
+          for (int f = 0; f < F; ++f) {
+            if (f < 2) {
+              id01[u][f] = raw[u][f];
+              hi = max(hi, (uint32_t)raw[u][f]);
+            } else {
+              const uint32_t d = (uint32_t)(raw[u][f] - ws32);
+              dm = max(dm, d);
+              pk[u][(f - 2) >> 2] |= d << (8 * ((f - 2) & 3));
+            }
           }
         }
-        miss |= m && (base + (int64_t)u * RPW + g < B);
+        miss = hi >= M32 || dm >= nhit;
+      } else {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+          for (int j = 0; j < PKW; ++j) pk[u][j] = 0u;
+          bool m = false;
+#pragma unroll
+          for (int f = 0; f < F; ++f) {
+            const int32_t id = clamp_id32(raw[u][f], M32);
+            bad |= id != raw[u][f];
+            if (f < 2) {
+              id01[u][f] = id;
+            } else {
+              const uint32_t d = (uint32_t)(id - ws32);
+              m |= d >= nhit;
+              pk[u][(f - 2) >> 2] |= (d < nm1 ? d : nm1) << (8 * ((f - 2) & 3));
+            }
+          }
+          miss |= m && (base + (int64_t)u * RPW + g < B);
+        }
       }
       // wave-uniform: some row of this wave-iteration needs a row outside the
-      // window -> the general loop takes over from this iteration on
+      // window (LEAN: or holds a bad id) -> the general loop takes over from
+      // this iteration on
       if (__ballot(miss) != 0) break;
 
       C c01[U][2];
@@ -364,8 +459,11 @@ __global__ __launch_bounds__(256) void fm_rows_fast_hot(
 #pragma unroll
       for (int u = 0; u < U; ++u) {
 #pragma unroll
-        for (int f = 0; f < 2; ++f)
-          c01[u][f].template load<NT01>(E + (int64_t)id01[u][f] * ROW_BYTES + sub * 16);
+        for (int f = 0; f < 2; ++f) {
+          // LEAN: the id is known to be in [0, M): zero-extended
+          const int64_t r = LEAN ? (int64_t)(uint32_t)id01[u][f] : (int64_t)id01[u][f];
+          c01[u][f].template load<NT01>(E + r * ROW_BYTES + sub * 16);
+        }
       }
       // `w` of the user and item from global memory into lanes sub = 0, 1
       // (fields 0, 1) of wg: by scalar loads (HHFM_K1_W_SCALAR), else by one
@@ -405,6 +503,8 @@ __global__ __launch_bounds__(256) void fm_rows_fast_hot(
         for (int u = 0; u < U; ++u) wg[u] = w[sub == 1 ? id01[u][1] : id01[u][0]];
       }
 
+      // the next iteration's ids (rows past B read row 0; where the next is
+      // no full iteration this loop does not use them)
       load_ids<F, U, false>(raw, idx, base + stride, B, g, RPW, F);
 
 #pragma unroll
@@ -420,7 +520,7 @@ __global__ __launch_bounds__(256) void fm_rows_fast_hot(
         // the row sum is reduced before the `w` terms are formed: stepping
         // the two sums together fills the DPP hazard slots but ran 0.45 %
         // slower and takes F = 6 bf16 past 168 VGPRs (profiles/k1_consume_ab.txt)
-        float t = group_sum_dpp<LPR>(fm_chunk_term<F>(c));
+        float t = group_sum_dpp<LPR>(fm_chunk_term<F, C, PK>(c));
         float fb = 0.f;
         if constexpr (HAS_W) {
           float wv = 0.f;
@@ -438,7 +538,7 @@ __global__ __launch_bounds__(256) void fm_rows_fast_hot(
           fb = group_sum_dpp<LPR>(wv);
         }
         const int64_t row = base + (int64_t)u * RPW + g;
-        if (sub == 0 && row < B) out[row] = (t + fb) + w0;
+        if (sub == 0 && (LEAN || row < B)) out[row] = (t + fb) + w0;
       }
     }
   }
@@ -488,7 +588,7 @@ __global__ __launch_bounds__(256) void fm_rows_fast_hot(
       load_ids_slots<F, U, UG>(raw, idx, nbase, nu0, B, g, RPW);
 #pragma unroll
       for (int u = 0; u < UG; ++u) {
-        float t = group_sum_dpp<LPR>(fm_chunk_term<F>(c[u]));
+        float t = group_sum_dpp<LPR>(fm_chunk_term<F, C, PK>(c[u]));
         float fb = 0.f;
         if constexpr (HAS_W) fb = group_sum_dpp<LPR>(wv[u]);
         const int64_t row = base + (int64_t)(u0 + u) * RPW + g;

@@ -4,6 +4,9 @@ Scoring runs on the gfx950 kernels of afm.hip (exact-fp32 MFMA):
   * ``score_rows`` / ``sess.run(model.out)`` -> hhfm_afm_forward (AFM.py:103-142)
   * ``topk(A, tp)`` -> hhfm_afm_catalog_topk (AFM.py:209-246)
   * ``partial_fit(data)`` -> hhfm_afm_train_step (AFM.py:144-156, 205-207)
+With ``attention=0`` (the model without the attention net, include/hhfm.h "AFM
+without attention") the three go to hhfm_fm_score_rows_scaled (scale = the
+prediction vector), hhfm_afm_noatt_catalog_topk and hhfm_afm_noatt_train_step.
 """
 from __future__ import annotations
 
@@ -64,8 +67,6 @@ class AFM(ScoringModel):
         self.optimizer_type = optimizer_type
         self.decay = decay
         self.u_f = valid_dimension - 1
-        if not attention:
-            raise NotImplementedError("the kernels implement attention=1 (the reference default)")
         self._setup_device(device, table_dtype)
         self._init_graph()
 
@@ -79,8 +80,15 @@ class AFM(ScoringModel):
 
     def _initialize_weights(self):
         """AFM.py:173-201 (attention weights glorot-normal from a seeded RNG)."""
-        rng = np.random.default_rng(self.random_seed)
         A, k = self.hidden_factor
+        if not self.attention:   # AFM.py:173-201 with self.attention false: four variables
+            return {
+                "feature_embeddings": self._normal((self.features_M, k), 0.01, self.random_seed),
+                "feature_bias": torch.zeros(self.features_M, 1, device=self.device),
+                "bias": torch.zeros((), device=self.device),
+                "prediction": torch.ones(k, 1, device=self.device),
+            }
+        rng = np.random.default_rng(self.random_seed)
         glorot = np.sqrt(2.0 / (A + k))
         t = lambda a: torch.from_numpy(np.asarray(a, np.float32)).to(self.device)  # noqa: E731
         return {
@@ -98,8 +106,15 @@ class AFM(ScoringModel):
         return (W["attention_W"].t().contiguous(), W["attention_b"].reshape(-1).contiguous(),
                 W["attention_p"].reshape(-1).contiguous(), W["prediction"].reshape(-1).contiguous())
 
+    def _P(self):
+        return self.weights["prediction"].reshape(-1).contiguous()
+
     def score_rows(self, X) -> np.ndarray:
         idx = self._idx(X)
+        if not self.attention:   # out = Σ_c P_c·½(s² − q) + Σw + w0
+            out = ops.fm_score_rows(idx, self.table, self.weights["feature_bias"].reshape(-1),
+                                    float(self.weights["bias"]), scale=self._P())
+            return self._np_out(out)
         Wt, b, p, P = self._att()
         out = ops.afm_forward(idx, self.table, self.weights["feature_bias"].reshape(-1),
                               float(self.weights["bias"]), Wt, b, p, P)
@@ -107,7 +122,14 @@ class AFM(ScoringModel):
 
     def catalog_topk(self, q, begin, count, K):
         """Top-K of items [begin, begin+count) by the attention score of
-        AFM.py:209-246 -> (scores, global item offsets) device tensors [B, K]."""
+        AFM.py:209-246 -> (scores, global item offsets) device tensors [B, K].
+        With attention=0 the score is ``out`` of the row with column 1 replaced
+        by the item (this library's definition: the reference's topk raises
+        KeyError('attention_W') there)."""
+        if not self.attention:
+            return ops.afm_noatt_catalog_topk(
+                q, self.table, self.weights["feature_bias"].reshape(-1),
+                float(self.weights["bias"]), self._P(), self.n_user + begin, count, int(K), begin)
         Wt, b, p, P = self._att()
         return ops.afm_catalog_topk(q, self.table, self.weights["feature_bias"].reshape(-1),
                                     Wt, b, p, P, self.n_user + begin, count, int(K), begin)
@@ -123,8 +145,11 @@ class AFM(ScoringModel):
 
     def partial_fit(self, data):
         """AFM.py:205-207 -> hhfm_afm_train_step (loss, then the update);
-        hhfm_afm_train_step_det when ``deterministic``."""
-        from .training import afm_partial_fit
+        hhfm_afm_train_step_det when ``deterministic``; the hhfm_afm_noatt_*
+        steps with attention=0."""
+        from .training import afm_noatt_partial_fit, afm_partial_fit
+        if not self.attention:
+            return afm_noatt_partial_fit(self, data)
         return afm_partial_fit(self, data)
 
 

@@ -127,6 +127,56 @@ __global__ __launch_bounds__(256) void catalog_queries(
   }
 }
 
+// AFM without attention (include/hhfm.h "AFM without attention"): the query
+// side of hhfm_afm_noatt_catalog_topk.  q_b = Σ_{f≠1} E[x_bf] over the F
+// columns of the query but the item's,
+//   H[b][c] = P_c·q_bc     cst[b] = Σ_c P_c·½(q_bc² − Σ_{f≠1} e_bf,c²) + Σ_{f≠1} w[x_bf] + w0
+// so that the main kernels' FM form H·E[i] + w[i] + cst is `out` of the row
+// with column 1 replaced by item i.  Zeros from B up to Bpad.
+struct NoAttQuery {
+  const float* P;   // [k] fp32 (the prediction vector)
+  float w0;
+};
+
+template <bool BF16>
+__global__ __launch_bounds__(256) void afm_noatt_queries(
+    const int32_t* __restrict__ qidx, int64_t B, int64_t Bpad, int F,
+    const char* __restrict__ E, int64_t M, int k, const float* __restrict__ w, NoAttQuery nq,
+    float* __restrict__ H, float* __restrict__ cst) {
+  const int lane = lane_id();
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  const int esz = BF16 ? 2 : 4;
+  for (int64_t b = wave; b < Bpad; b += nwave) {
+    float part = 0.f;
+    if (b < B) {
+      const int32_t* p = qidx + b * (int64_t)F;
+      for (int e = lane; e < k; e += kWave) {
+        float s = 0.f, q = 0.f;
+        for (int f = 0; f < F; ++f) {
+          if (f == kItemCol) continue;
+          const char* r = E + (int64_t)clamp_id(p[f], M) * k * esz;
+          const float v = BF16 ? bf16_to_f32(reinterpret_cast<const uint16_t*>(r)[e])
+                               : reinterpret_cast<const float*>(r)[e];
+          s += v;
+          q += v * v;
+        }
+        const float pc = nq.P[e];
+        H[b * k + e] = pc * s;
+        part += pc * (0.5f * (s * s - q));
+      }
+      part = group_sum<kWave>(part);
+      float fb = 0.f;
+      for (int f = 0; f < F; ++f)
+        if (f != kItemCol && w) fb += w[clamp_id(p[f], M)];
+      part = (part + fb) + nq.w0;
+    } else {
+      for (int e = lane; e < k; e += kWave) H[b * k + e] = 0.f;
+    }
+    if (lane == 0) cst[b] = part;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // 2. main kernel
 // ---------------------------------------------------------------------------
@@ -1419,7 +1469,7 @@ static int catalog_topk_impl(
     int32_t global_item_base, int32_t K, float* top_score, int32_t* top_idx,
     void* workspace, size_t ws_bytes, int32_t plan, int32_t pooling, int32_t* status,
     void* stream, bool two_way = false, int32_t pooling2 = 0,
-    const Cars2Query* cars2 = nullptr) {
+    const Cars2Query* cars2 = nullptr, const NoAttQuery* noatt = nullptr) {
   PoolModes pm;
   PoolModes2 pm2{};
   if (!pooling_unpack(pooling, pm)) return HHFM_EINVAL;
@@ -1473,7 +1523,7 @@ static int catalog_topk_impl(
   // (two-way has no form of the fused kernel: it always forms H with
   // catalog_queries over TwoWayFeature and runs the main kernels below)
   const bool fused_size = item_count <= 8192 || (plan & HHFM_PLAN_FUSED);
-  if (!two_way && !cars2 && p.dense && fused_size && K <= 32 && KT <= 8 && p.fS <= kFusedMaxS &&
+  if (!two_way && !cars2 && !noatt && p.dense && fused_size && K <= 32 && KT <= 8 && p.fS <= kFusedMaxS &&
       (B + kQPerWave - 1) / kQPerWave <= kFusedMaxGroups &&
       ctx_end - ctx_begin <= kFusedMaxCtx && time_end - time_begin <= kFusedMaxCtx &&
       !(plan & (HHFM_PLAN_GEMM | HHFM_PLAN_STORE))) {
@@ -1508,6 +1558,10 @@ static int catalog_topk_impl(
     };
     if (cars2)   // CARS2: h = u + GB[m], cst = u·GA[m]; the main kernels' FM form with w = NULL
       cars2_launch_queries(qidx, B, p.Bpad, Eb, bf16, features_M, k, *cars2, H, cst, status, st);
+    else if (noatt)   // attention=0: h = P ⊙ q, cst the item-free part of out; FM form with w
+      hipLaunchKernelGGL(bf16 ? afm_noatt_queries<true> : afm_noatt_queries<false>,
+                         dim3((int)blocks), dim3(256), 0, st, qidx, B, p.Bpad, ncols, Eb,
+                         features_M, k, w, *noatt, H, cst);
     else if (two_way)
       queries(TwoWayFeature{pm2});
     else if (pooling != 0)
@@ -1682,6 +1736,25 @@ extern "C" int hhfm_cars2_catalog_topk(
   return catalog_topk_impl(q, B, 2, HHFM_MODE_FM, 0, 0, 0, 0, 0, UI, n_ui, D, dtype, nullptr,
                            item_row_begin, item_count, global_item_base, K, top_score, top_idx,
                            workspace, ws_bytes, plan, 0, status, stream, false, 0, &cq);
+}
+
+// AFM.topk with attention=0 (include/hhfm.h "AFM without attention"): H and cst
+// from afm_noatt_queries, then the main kernels unchanged on their FM form with
+// the items' w; never the small-catalog fused kernel (its step 0 forms FM's
+// own h).  The ids of every query column but the item's are checked.
+extern "C" int hhfm_afm_noatt_catalog_topk(
+    const int32_t* qidx, int64_t B, int32_t F, const void* E, int64_t features_M, int32_t k,
+    int32_t dtype, const float* w, float w0, const float* P, int32_t item_row_begin,
+    int32_t item_count, int32_t global_item_base, int32_t K, float* top_score,
+    int32_t* top_idx, void* workspace, size_t ws_bytes, int32_t plan, int32_t* status,
+    void* stream) {
+  if (F < 2) return HHFM_EINVAL;
+  if (B > 0 && !P) return HHFM_EINVAL;
+  const NoAttQuery nq{P, w0};
+  return catalog_topk_impl(qidx, B, F, HHFM_MODE_FM, kUserCol, 2, F, 0, 0, E, features_M, k,
+                           dtype, w, item_row_begin, item_count, global_item_base, K, top_score,
+                           top_idx, workspace, ws_bytes, plan, 0, status, stream, false, 0,
+                           nullptr, &nq);
 }
 
 #if HHFM_FUSED_TIMING

@@ -808,6 +808,76 @@ PYBIND11_MODULE(_hhfm, m) {
           check(rc, "hhfm_afm_train_step_ex");
         });
 
+  // AFM without attention (include/hhfm.h "AFM without attention")
+  m.def("afm_noatt_catalog_topk",
+        [](uptr qidx, int64_t B, int F, uptr E, int64_t M, int k, int dtype, uptr w, float w0,
+           uptr Pv, int item_row_begin, int item_count, int global_item_base, int K,
+           uptr top_score, uptr top_idx, uptr ws, size_t ws_bytes, int plan, uptr status,
+           uptr stream) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_afm_noatt_catalog_topk(P<const int32_t>(qidx), B, F, P<const void>(E), M, k,
+                                             dtype, P<const float>(w), w0, P<const float>(Pv),
+                                             item_row_begin, item_count, global_item_base, K,
+                                             P<float>(top_score), P<int32_t>(top_idx), P<void>(ws),
+                                             ws_bytes, plan, P<int32_t>(status), P<void>(stream));
+          }
+          check(rc, "hhfm_afm_noatt_catalog_topk");
+        });
+
+  m.def("afm_noatt_train_workspace", [](int64_t M, int k) {
+    size_t ws = 0;
+    check(hhfm_afm_noatt_train_workspace(M, k, &ws), "hhfm_afm_noatt_train_workspace");
+    return ws;
+  });
+
+  m.def("afm_noatt_train_det_scratch", [](int64_t B, int F, int k, int64_t M) {
+    size_t n = 0;
+    check(hhfm_afm_noatt_train_det_scratch(B, F, k, M, &n), "hhfm_afm_noatt_train_det_scratch");
+    return n;
+  });
+
+  m.def("afm_noatt_train_step",
+        [](uptr idx, uptr y, int64_t B, int F, uptr E, uptr w, uptr w0, uptr Pv, int64_t M, int k,
+           float lr, int opt, float keep_afm, uint64_t seed, std::vector<uptr> acc, uptr ws,
+           size_t ws_bytes, uptr loss, uptr stream) {
+          if (opt != HHFM_OPT_SGD && acc.size() != 4)
+            throw py::value_error("acc needs 4 slot arrays (E, w, w0, P)");
+          std::vector<float*> av(acc.size());
+          for (size_t i = 0; i < acc.size(); ++i) av[i] = P<float>(acc[i]);
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_afm_noatt_train_step(P<const int32_t>(idx), P<const float>(y), B, F,
+                                           P<float>(E), P<float>(w), P<float>(w0), P<float>(Pv), M,
+                                           k, lr, opt, keep_afm, seed,
+                                           av.empty() ? nullptr : av.data(), P<void>(ws), ws_bytes,
+                                           P<float>(loss), P<void>(stream));
+          }
+          check(rc, "hhfm_afm_noatt_train_step");
+        });
+
+  m.def("afm_noatt_train_step_det",
+        [](uptr idx, uptr y, int64_t B, int F, uptr E, uptr w, uptr w0, uptr Pv, int64_t M, int k,
+           float lr, int opt, float keep_afm, uint64_t seed, std::vector<uptr> acc, uptr ws,
+           size_t ws_bytes, uptr scratch, size_t scratch_bytes, uptr loss, uptr stream) {
+          if (opt != HHFM_OPT_SGD && acc.size() != 4)
+            throw py::value_error("acc needs 4 slot arrays (E, w, w0, P)");
+          std::vector<float*> av(acc.size());
+          for (size_t i = 0; i < acc.size(); ++i) av[i] = P<float>(acc[i]);
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_afm_noatt_train_step_det(
+                P<const int32_t>(idx), P<const float>(y), B, F, P<float>(E), P<float>(w),
+                P<float>(w0), P<float>(Pv), M, k, lr, opt, keep_afm, seed,
+                av.empty() ? nullptr : av.data(), P<void>(ws), ws_bytes, P<void>(scratch),
+                scratch_bytes, P<float>(loss), P<void>(stream));
+          }
+          check(rc, "hhfm_afm_noatt_train_step_det");
+        });
+
   // the deterministic AFM / DeepFM steps (include/hhfm.h)
   m.def("afm_train_det_scratch", [](int64_t B, int F, int k, int A, int64_t M) {
     size_t n = 0;

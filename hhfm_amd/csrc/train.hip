@@ -21,6 +21,9 @@
 //                         heads (DFM.py:131-152): the DeepFM step under a head word
 //   hhfm_cars2_train_step replaces the same for CARS2 (Newcode/CARS2.py:87,
 //                         :103-136, :167-170); its kernels are in cars2.hip
+//   hhfm_afm_noatt_train_step / _det  AFM with `--attention 0` (AFM.py:103-148
+//                         with self.attention false): FM's k-vector weighted by
+//                         the prediction vector ("AFM without attention" below)
 //
 // One wave per batch row computes the forward score(s) and scatters the
 // gradient of the row's loss into dense fp32 gradient buffers with float
@@ -2007,6 +2010,191 @@ __global__ __launch_bounds__(256) void fm_bn_scatter(
   }
 }
 
+// ---------------------------------------------------------------------------
+// AFM without attention (hhfm_afm_noatt_train_step; include/hhfm.h "AFM without
+// attention", AFM.py:103-148 with self.attention false): FM's k-vector
+// x_c = ½(s² − q) weighted by the prediction vector P,
+//   out = Σ_c d_c·P_c + Σ_f w + w0     d_c = x_c (/ keep · bin_c)
+// with tf.nn.dropout on the k-vector (dropout.h site 2, keep1, the row index
+// the batch row) and no regulariser.  One wave per row, lane l the columns
+// l + 64·j (k <= 256: one Philox block per lane serves them), the forward with
+// fm_train_rows's expressions for s and q in field order.
+// DET false: dE / dw by float atomics; a lane adds g·d_c of its rows in a
+// register (fp32), the workgroup's waves meet through LDS and ONE double
+// atomicAdd per workgroup and column goes to dP64 (bn_block_add, as FM-BN's
+// dγ); a wave adds its rows' r²/2 in double and g in fp32 and sends one atomic
+// each when it is done.
+// DET true (hhfm_afm_noatt_train_step_det): no atomics — S_b[c] (Sb [B][k];
+// under dropout bin_b[c] follows, [B][k] more), v_bc = g_b·d_bc (Vb [B][k], for
+// det_columns), g_b and the row's loss in double are stored.
+// ---------------------------------------------------------------------------
+constexpr int kNoAttMaxK = 256;
+
+template <bool DROP, bool DET>
+__global__ __launch_bounds__(256) void afm_noatt_train_rows(
+    const int32_t* __restrict__ idx, const float* __restrict__ y, int64_t B, int F,
+    const float* __restrict__ E, const float* __restrict__ w, const float* __restrict__ w0,
+    const float* __restrict__ P, int64_t M, int k, float* __restrict__ dE,
+    float* __restrict__ dw, float* __restrict__ scal, double* __restrict__ dP64, DropoutArgs dr,
+    float* __restrict__ gb, double* __restrict__ lossb, float* __restrict__ Sb,
+    float* __restrict__ Vb) {
+#pragma clang fp contract(off)
+  constexpr int NC = kNoAttMaxK / kWave;
+  __shared__ float red[4][kWave];
+  const int l = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  float accP[NC];
+#pragma unroll
+  for (int j = 0; j < NC; ++j) accP[j] = 0.f;
+  double lossw = 0.0;
+  float gw = 0.f;
+  for (int64_t b = wave; b < B; b += nwave) {
+    const int32_t* x = idx + b * F;
+    float sv[NC], dv[NC], mb[NC];
+    [[maybe_unused]] Philox4 blk;
+    if constexpr (DROP) blk = dropout_block(dr.key0, dr.key1, kDropSiteAfmVec, b, l);
+    float t = 0.f;
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+      const int c = l + kWave * j;
+      sv[j] = dv[j] = 0.f;
+      mb[j] = 1.f;
+      if (c < k) {
+        float s = 0.f, q = 0.f;
+        for (int f = 0; f < F; ++f) {
+          const float v = E[(int64_t)clamp_id(x[f], M) * k + c];
+          s += v;
+          q += v * v;
+        }
+        float xv = 0.5f * (s * s - q);
+        if constexpr (DROP) {
+          mb[j] = dropout_binary(dr.keep1, blk.v[j]);
+          xv = xv / dr.keep1 * mb[j];
+        }
+        sv[j] = s;
+        dv[j] = xv;
+        t += xv * P[c];
+      }
+    }
+    t = group_sum<kWave>(t);
+    float fb = 0.f;
+    for (int f = 0; f < F; ++f) fb += w[clamp_id(x[f], M)];
+    const float out = (t + fb) + w0[0];
+    const float r = y[b] - out;        // l2_loss(y - out) = r²/2   AFM.py:148
+    const float g = -r;
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+      const int c = l + kWave * j;
+      if (c < k) {
+        const float v = g * dv[j];     // the row's term of dP_c
+        if constexpr (DET) {
+          Sb[b * k + c] = sv[j];
+          if constexpr (DROP) Sb[(B + b) * k + c] = mb[j];
+          Vb[b * k + c] = v;
+        } else {
+          accP[j] += v;
+          if (!DROP || mb[j] != 0.f) {   // a dropped column scatters nothing
+            float gc = g * P[c];
+            if constexpr (DROP) gc = gc * mb[j] / dr.keep1;
+            for (int f = 0; f < F; ++f) {
+              const int64_t id = clamp_id(x[f], M);
+              atomicAdd(dE + id * k + c, gc * (sv[j] - E[id * k + c]));
+            }
+          }
+        }
+      }
+    }
+    if constexpr (DET) {
+      if (l == 0) {
+        gb[b] = g;
+        lossb[b] = 0.5 * ((double)r * (double)r);
+      }
+    } else {
+      for (int f = l; f < F; f += kWave) atomicAdd(dw + clamp_id(x[f], M), g);
+      gw += g;
+      lossw += 0.5 * ((double)r * (double)r);
+    }
+  }
+  if constexpr (DET) return;
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    if (j * kWave >= k) break;
+    bn_block_add(red, accP[j], l + kWave * j, k, dP64);
+  }
+  if (l == 0 && wave < B) {   // g and the loss are wave-uniform
+    atomicAdd(scal + kScalBiasGrad, gw);
+    atomicAdd(scal_loss64(scal), lossw);
+  }
+}
+
+// dP[c] = the double column sum rounded once; the sums are left zeroed
+__global__ __launch_bounds__(256) void afm_noatt_dp(int k, double* __restrict__ dP64,
+                                                    float* __restrict__ dP) {
+  for (int c = threadIdx.x; c < k; c += blockDim.x) {
+    dP[c] = (float)dP64[c];
+    dP64[c] = 0.0;
+  }
+}
+
+// The occurrence o = b·F + f of the deterministic step: FmContrib with the
+// column weight, gc = g_b·P_c (· bin / keep under dropout), contribution
+// gc·(S_b[c] − e); a dropped column adds nothing; dw: g_b.
+template <bool DROP>
+struct NoAttContrib {
+  static constexpr bool kBias = true;
+  const float* g;
+  const float* S;   // S [B][k], then (DROP) bin [B][k]
+  const float* P;
+  int64_t B;
+  int F, k;
+  float keep;
+  struct Occ {
+    int b;
+    float g;
+  };
+  HHFM_DEV Occ load(int o) const {
+    const int b = o / F;
+    return Occ{b, g[b]};
+  }
+  HHFM_DEV Occ lane(const Occ& oc, int u) const { return Occ{lane_i(oc.b, u), lane_f(oc.g, u)}; }
+  HHFM_DEV float bias(const Occ& oc) const { return oc.g; }
+  HHFM_DEV bool value(const Occ& oc, int c, float e, float& out) const {
+#pragma clang fp contract(off)
+    float gc = oc.g * P[c];
+    bool kept = true;
+    if constexpr (DROP) {
+      const float bin = S[((int64_t)B + oc.b) * k + c];
+      kept = bin != 0.f;
+      gc = gc * bin / keep;
+    }
+    out = gc * (S[(int64_t)oc.b * k + c] - e);
+    return kept;
+  }
+};
+
+// The workspace: fm_train_plan's layout, then dP [k] floats and the column
+// sums dP64 [k] doubles — all zero-filled once by the caller and left zeroed.
+struct NoAttPlan {
+  FmTrainPlan fm;
+  size_t off_dP, off_dP64, bytes;
+};
+
+static NoAttPlan afm_noatt_plan(int64_t M, int k) {
+  NoAttPlan p;
+  p.fm = fm_train_plan(M, k);
+  p.off_dP = al256(p.fm.bytes);
+  p.off_dP64 = al256(p.off_dP + (size_t)k * 4);
+  p.bytes = al256(p.off_dP64 + (size_t)k * 8);
+  return p;
+}
+
+// S and bin [2][B][k] in `rowvec`, v [B][k] in `heads`; there is no Σvar²
+static bool afm_noatt_det_plan(int64_t B, int F, int k, int64_t M, DetPlan& d) {
+  if (k < 1 || B < 0 || M < 1 || B > 0x7fffffff) return false;
+  return det_plan_regions(B, F, M, B * 2 * k, 0, 0, B * k, d);
+}
+
 // binary[r][e] = the train kernels' dropout decision (dropout.h) as 0.f / 1.f
 __global__ __launch_bounds__(256) void dropout_mask(DropoutArgs dr, int site, int64_t rows, int n,
                                                     float* __restrict__ binary) {
@@ -2896,3 +3084,107 @@ extern "C" int hhfm_afm_train_det_scratch(int64_t B, int32_t F, int32_t k, int32
   return HHFM_OK;
 }
 
+
+extern "C" int hhfm_afm_noatt_train_workspace(int64_t features_M, int32_t k, size_t* ws_bytes) {
+  if (!ws_bytes || features_M < 1 || k < 1) return HHFM_EINVAL;
+  if (k > kNoAttMaxK) return HHFM_EUNSUPPORTED;
+  *ws_bytes = afm_noatt_plan(features_M, k).bytes;
+  return HHFM_OK;
+}
+
+// The attention=0 step: the default path (det false; scratch unused), or the
+// deterministic one on `scratch` (hhfm_afm_noatt_train_det_scratch bytes).
+static int afm_noatt_step_impl(const int32_t* idx, const float* y, int64_t B, int32_t F, float* E,
+                               float* w, float* w0, float* P, int64_t features_M, int32_t k,
+                               float lr, int32_t optimizer, float keep_afm, uint64_t seed,
+                               float* const* acc, void* workspace, size_t ws_bytes, bool det,
+                               void* scratch, size_t scratch_bytes, float* loss, void* stream) {
+  if (B < 0 || F < 1 || k < 1 || features_M < 1 || !keep_ok(keep_afm)) return HHFM_EINVAL;
+  if (k > kNoAttMaxK) return HHFM_EUNSUPPORTED;
+  if (!opt_ok(optimizer)) return HHFM_EUNSUPPORTED;
+  if (!E || !w || !w0 || !P || !loss || !workspace) return HHFM_EINVAL;
+  if (B > 0 && (!idx || !y)) return HHFM_EINVAL;   // an empty batch reads no rows
+  if (!slots_ok(optimizer, acc, 4)) return HHFM_EINVAL;   // acc: E, w, w0, P
+  const NoAttPlan p = afm_noatt_plan(features_M, k);
+  if (ws_bytes < p.bytes) return HHFM_EWORKSPACE;
+  if (reinterpret_cast<uintptr_t>(workspace) & 7) return HHFM_EINVAL;   // the double sums
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  DetPlan d{};
+  if (det) {
+    if (!afm_noatt_det_plan(B, F, k, features_M, d) || !scratch) return HHFM_EINVAL;
+    if (scratch_bytes < d.bytes) return HHFM_EWORKSPACE;
+    if (const int rc = det_sort_fits(d, st)) return rc;
+  }
+  char* base = reinterpret_cast<char*>(workspace);
+  float* ws = reinterpret_cast<float*>(workspace);
+  float* scal = ws + p.fm.off_scal;
+  float* dP = reinterpret_cast<float*>(base + p.off_dP);
+  double* dP64 = reinterpret_cast<double*>(base + p.off_dP64);
+  char* sc = reinterpret_cast<char*>(scratch);
+  const bool drop = keep_afm < 1.f;
+  const DropoutArgs dr = dropout_args(1.f, keep_afm, seed);
+  if (B > 0 && !det) {
+    auto rows = drop ? afm_noatt_train_rows<true, false> : afm_noatt_train_rows<false, false>;
+    hipLaunchKernelGGL(rows, dim3(bn_grid(B)), dim3(256), 0, st, idx, y, B, F, E, w, w0, P,
+                       features_M, k, ws + p.fm.off_dE, ws + p.fm.off_dw, scal, dP64, dr, nullptr,
+                       nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(afm_noatt_dp, dim3(1), dim3(256), 0, st, k, dP64, dP);
+  } else if (B > 0) {
+    float* gb = reinterpret_cast<float*>(sc + d.g);
+    float* Sb = reinterpret_cast<float*>(sc + d.rowvec);
+    float* Vb = reinterpret_cast<float*>(sc + d.heads);
+    auto rows = drop ? afm_noatt_train_rows<true, true> : afm_noatt_train_rows<false, true>;
+    hipLaunchKernelGGL(rows, dim3(grid_for_n(B * 64)), dim3(256), 0, st, idx, y, B, F, E, w, w0, P,
+                       features_M, k, nullptr, nullptr, nullptr, nullptr, dr, gb,
+                       reinterpret_cast<double*>(sc + d.loss), Sb, Vb);
+    hipLaunchKernelGGL(det_columns, dim3(k), dim3(256), 0, st, Vb, B, (int64_t)k, dP);
+    const OccSource src{idx, nullptr, F, 0, 0, 0, 0, 0};
+    const int rc =
+        drop ? det_scatter(d, sc, src, F, B, features_M, E, k, ws + p.fm.off_dE, ws + p.fm.off_dw,
+                           gb, scal, NoAttContrib<true>{gb, Sb, P, B, F, k, keep_afm}, st)
+             : det_scatter(d, sc, src, F, B, features_M, E, k, ws + p.fm.off_dE, ws + p.fm.off_dw,
+                           gb, scal, NoAttContrib<false>{gb, Sb, P, B, F, k, keep_afm}, st);
+    if (rc != 0) return rc;
+  }
+  // E and w have IndexedSlices gradients (sparse), w0 and P dense; no variable
+  // carries an l2 term (AFM.py:148) and the loss none
+  auto slot = [&](int i) { return slot_of(optimizer, acc, i); };
+  const OptVar vars[] = {{E, ws + p.fm.off_dE, slot(0), features_M * k, 0.f, k, true, false},
+                         {w, ws + p.fm.off_dw, slot(1), features_M, 0.f, 1, true, false},
+                         {w0, scal + kScalBiasGrad, slot(2), 1, 0.f, 1, false, false},
+                         {P, dP, slot(3), k, 0.f, 1, false, false}};
+  uint8_t* touched = reinterpret_cast<uint8_t*>(ws + p.fm.off_touch);
+  return optimizer_tail(vars, (int)std::size(vars), {{idx, B * F}}, features_M, optimizer, lr,
+                        scal, touched, 0.f, loss, st);
+}
+
+extern "C" int hhfm_afm_noatt_train_step(const int32_t* idx, const float* y, int64_t B, int32_t F,
+                                         float* E, float* w, float* w0, float* P,
+                                         int64_t features_M, int32_t k, float lr,
+                                         int32_t optimizer, float keep_afm, uint64_t seed,
+                                         float* const* acc, void* workspace, size_t ws_bytes,
+                                         float* loss, void* stream) {
+  return afm_noatt_step_impl(idx, y, B, F, E, w, w0, P, features_M, k, lr, optimizer, keep_afm,
+                             seed, acc, workspace, ws_bytes, false, nullptr, 0, loss, stream);
+}
+
+extern "C" int hhfm_afm_noatt_train_step_det(const int32_t* idx, const float* y, int64_t B,
+                                             int32_t F, float* E, float* w, float* w0, float* P,
+                                             int64_t features_M, int32_t k, float lr,
+                                             int32_t optimizer, float keep_afm, uint64_t seed,
+                                             float* const* acc, void* workspace, size_t ws_bytes,
+                                             void* scratch, size_t scratch_bytes, float* loss,
+                                             void* stream) {
+  return afm_noatt_step_impl(idx, y, B, F, E, w, w0, P, features_M, k, lr, optimizer, keep_afm,
+                             seed, acc, workspace, ws_bytes, true, scratch, scratch_bytes, loss,
+                             stream);
+}
+
+extern "C" int hhfm_afm_noatt_train_det_scratch(int64_t B, int32_t F, int32_t k,
+                                                int64_t features_M, size_t* bytes) {
+  DetPlan d;
+  if (!bytes || F < 1 || !afm_noatt_det_plan(B, F, k, features_M, d)) return HHFM_EINVAL;
+  if (k > kNoAttMaxK) return HHFM_EUNSUPPORTED;
+  *bytes = d.bytes;
+  return HHFM_OK;
+}

@@ -620,6 +620,35 @@ def afm_catalog_topk(qidx: torch.Tensor, E: torch.Tensor, w: torch.Tensor, Wt: t
     return top_s, top_i
 
 
+def afm_noatt_catalog_topk(qidx: torch.Tensor, E: torch.Tensor, w: Optional[torch.Tensor],
+                           w0: float, P: torch.Tensor, item_row_begin: int, item_count: int,
+                           K: int, global_item_base: int = 0,
+                           status: Optional[torch.Tensor] = None, plan: int = 0):
+    """AFM.topk with attention=0 (include/hhfm.h "AFM without attention") ->
+    (scores [B,K], ids [B,K]): the score of item i is ``out`` of the query row
+    with column 1 replaced by i — this library's definition, the reference's
+    topk raises KeyError here.  ``plan`` as in :func:`catalog_topk`."""
+    _idx(qidx, "qidx")
+    dev = _need_cuda(qidx, E, w, P)
+    B, F = qidx.shape
+    M, k = E.shape
+    if P.dtype != torch.float32 or P.numel() != k:
+        raise ValueError("P must be float32 with k entries")
+    if w is not None and (w.dtype != torch.float32 or w.numel() != M):
+        raise ValueError("w must be float32 with features_M entries")
+    nat = native()
+    st = _stream(dev)
+    ws = _catalog_workspace(dev, st, nat.catalog_topk_workspace(B, item_count, k, K))
+    top_s = torch.empty(B, K, dtype=torch.float32, device=dev)
+    top_i = torch.empty(B, K, dtype=torch.int32, device=dev)
+    nat.afm_noatt_catalog_topk(qidx.data_ptr(), B, F, E.data_ptr(), M, k, _dtype_code(E),
+                               0 if w is None else w.data_ptr(), float(w0), P.data_ptr(),
+                               item_row_begin, item_count, global_item_base, K,
+                               top_s.data_ptr(), top_i.data_ptr(), ws.data_ptr(), ws.numel(),
+                               int(plan), _status_ptr(status), st)
+    return top_s, top_i
+
+
 # ---- H5 / H3: harness membership test and metric walk ------------------------
 def pf_contains(keys: torch.Tensor, codes: torch.Tensor, rows: torch.Tensor, item_col: int,
                 cand: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -341,6 +341,38 @@ def afm_partial_fit(model, data) -> float:
     return float(st["loss"].item())
 
 
+def afm_noatt_partial_fit(model, data) -> float:
+    """AFM.partial_fit with attention=0 (AFM.py:103-148 with self.attention
+    false; include/hhfm.h "AFM without attention"): one TF step on the four
+    variables, loss l2_loss(y − out) without a regulariser; keep[0] is
+    validated and has no site, keep[1] drops the k-vector (AFM.py:134)."""
+    opt = _opt_code(model)
+    _, keep_afm = _keep(model.keep, 2)
+    W = model.weights
+    names = ["feature_embeddings", "feature_bias", "bias", "prediction"]
+    st = _state(model, names, opt)
+    X = model._idx(data["X"])
+    y = _labels(model, data)
+    B, F = X.shape
+    M, k = W["feature_embeddings"].shape
+    nat = native()
+    if st["ws"] is None:   # fixed: the layout does not depend on the batch
+        st["ws"] = _grow(None, nat.afm_noatt_train_workspace(M, k), 0, model.device)
+    ptr = lambda n: W[n].data_ptr()  # noqa: E731
+    args = (X.data_ptr(), y.data_ptr(), B, F, ptr("feature_embeddings"), ptr("feature_bias"),
+            ptr("bias"), ptr("prediction"), M, k, float(model.learning_rate), opt, keep_afm,
+            _next_seed(model, st), [st[n].data_ptr() for n in names] if opt != _SGD else [],
+            st["ws"].data_ptr(), st["ws"].numel())
+    tail = (st["loss"].data_ptr(), ops._stream(model.device))
+    if getattr(model, "deterministic", False):
+        sc = _det_scratch(model, st, B,
+                          size_fn=lambda b: nat.afm_noatt_train_det_scratch(b, F, k, M))
+        nat.afm_noatt_train_step_det(*args, sc.data_ptr(), sc.numel(), *tail)
+    else:
+        nat.afm_noatt_train_step(*args, *tail)
+    return float(st["loss"].item())
+
+
 def _log(tr, line):
     print(line)
     path = getattr(tr.args, "result_file", None)

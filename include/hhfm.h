@@ -523,6 +523,104 @@ int hhfm_afm_catalog_topk_ex(const int32_t* qidx, int64_t B, int32_t F, const vo
                              int32_t plan, void* workspace, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * AFM without attention — the reference's `--attention 0` (AFM.py:103-148
+ * with self.attention false; the AFM paper's ablation).  The model has four
+ * variables: the table E, w, w0 and the prediction vector P [k].  For a row
+ * of F ids x_0..x_{F-1}, e_f = E[x_f]:
+ *   x_c  = Σ_{i<j} e_i,c·e_j,c = ½[(Σ_f e_f,c)² − Σ_f e_f,c²]
+ *   d_c  = x_c / keep_afm · bin_c        tf.nn.dropout on the k-vector (AFM.py:134)
+ *   out  = Σ_c d_c·P_c + Σ_f w[x_f] + w0
+ *   loss = Σ_b (y_b − out_b)²/2          no regulariser, whatever lamda_attention
+ *                                        is (AFM.py:148)
+ * keep[0] (the attention's) has no site in this model.
+ *
+ * Row scores need no entry point of their own: hhfm_fm_score_rows_scaled with
+ * scale = P is `out` at keep = 1, for fp32 and bf16 tables.
+ *
+ * Catalog score.  The reference's topk raises KeyError('attention_W') here,
+ * so this is THIS LIBRARY'S definition: the score of item i for query row b
+ * is `out` (keep = 1) of the row with column 1 replaced by the item's table
+ * row — as with attention on, where the reference's topk ranks by `out`.
+ * Column 1 of the query is ignored, as in AFM.topk.
+ *   q_b   = Σ_{f≠1} E[x_bf]
+ *   score = (P ⊙ q_b)·E[i] + w[i] + cst_b
+ *   cst_b = Σ_c P_c·½(q_bc² − Σ_{f≠1} e_bf,c²) + Σ_{f≠1} w[x_bf] + w0
+ * top_score is that full value (not up to a per-query constant): it can be
+ * compared with the row score of the same row.  hhfm_afm_noatt_catalog_topk
+ * forms H = P ⊙ q and cst in a query kernel of its own and runs
+ * hhfm_catalog_topk_ex's plans on them (HHFM_MODE_FM's form: H·E[i] + w[i] +
+ * cst): the same workspace (hhfm_catalog_topk_workspace), item range
+ * arguments, K in [1, 64], plan flags, zero-prefix contract and status word
+ * (the ids of every query column but column 1), and the same k limits (fp32
+ * k in {8, .., 128}, bf16 k in {16, .., 256}, powers of two).  The
+ * small-catalog fused kernel is never taken (HHFM_PLAN_FUSED is accepted and
+ * falls through to the score-matrix path).  F >= 2; w may be NULL.
+ *
+ * Training.  hhfm_afm_noatt_train_step is one TF step on E, w, w0 and P; acc
+ * = slots of {E, w, w0, P} in that order (NULL under SGD).  No variable
+ * carries an l2 term, so E and w follow the IndexedSlices rules of "optimizer"
+ * below (sparse Momentum touches the batch's rows only, sparse Adam decays
+ * every row), w0 and P are dense.  With g_b = out_b − y_b, m_bc = bin_bc /
+ * keep_afm and s_bc = Σ_f e_bf,c:
+ *   dP_c = Σ_b g_b·x_bc·m_bc      dE[x_bf][c] += g_b·P_c·m_bc·(s_bc − e_bf,c)
+ *   dw[x_bf] += g_b               dw0 = Σ_b g_b
+ * The mask is "Training dropout"'s site 2 (n = k, r = the batch row) under the
+ * step's seed — AFM's own site, so keep_afm = 1 draws nothing.  dP is summed
+ * in fp32 inside a workgroup and in double across workgroups; the loss in
+ * double.  B = 0 is a step like any other: no row is touched, Adam's moments
+ * and powers advance, the loss is 0, idx / y may be NULL.
+ * Envelope: F >= 1, 1 <= k <= 256.  k > 256 is HHFM_EUNSUPPORTED, as is an
+ * unknown optimizer; F < 1, k < 1, B < 0, features_M < 1, a keep_afm that is
+ * NaN or outside (0, 1], a NULL parameter / loss / workspace, missing slots
+ * and a workspace not 8-byte aligned are HHFM_EINVAL, a short workspace
+ * HHFM_EWORKSPACE — all before any launch.  The workspace
+ * (hhfm_afm_noatt_train_workspace bytes: hhfm_train_workspace's layout, then
+ * dP [k] and its double sums) is zero-filled once and left zeroed but Adam's
+ * β powers; it does not depend on B.
+ *
+ * hhfm_afm_noatt_train_step_det: the same step under the promise of
+ * "Deterministic training steps" below, no float atomic:
+ *   dE[id][c], dw[id]   an occurrence is o = b·F + f (FM's order); its
+ *       contribution is gc·(S_b[c] − e) with gc = g_b·P_c (· bin / keep), to
+ *       dw[id] it is g_b; a dropped column adds nothing.  Each element is the
+ *       fp32 sum of the id's contributions in ascending o, started from the
+ *       first one.
+ *   dP[c]   the rows' values v_bc = g_b·(x_bc / keep · bin_bc) in the scalar
+ *       order: 256 partials, partial t = rows t, t + 256, ... ascending from
+ *       0, then the partials in ascending t from 0, all in fp32.
+ *   dw0, the loss   the scalar order on g_b (float) and g_b²/2 formed in
+ *       double, rounded to float once.  There is no Σ var².
+ * Every product above is rounded on its own (no fused multiply-add).
+ * `scratch` (hhfm_afm_noatt_train_det_scratch bytes, for that B or any smaller
+ * one) carries no state and need not be zeroed; the query runs on the host.
+ * The default step's checks come first, in their order; then a NULL scratch is
+ * HHFM_EINVAL and a too small one HHFM_EWORKSPACE (also at B = 0), and
+ * hipCUB's real temporary-storage figure is checked, before anything is
+ * launched: a refusal leaves every parameter, slot and the workspace
+ * untouched.  (numpy restatement: tests/train_det_noatt_ref.py.)
+ * ---------------------------------------------------------------------- */
+int hhfm_afm_noatt_catalog_topk(const int32_t* qidx, int64_t B, int32_t F, const void* E,
+                                int64_t features_M, int32_t k, int32_t dtype, const float* w,
+                                float w0, const float* P, int32_t item_row_begin,
+                                int32_t item_count, int32_t global_item_base, int32_t K,
+                                float* top_score, int32_t* top_idx, void* workspace,
+                                size_t ws_bytes, int32_t plan, int32_t* status, void* stream);
+int hhfm_afm_noatt_train_workspace(int64_t features_M, int32_t k, size_t* ws_bytes);
+int hhfm_afm_noatt_train_step(const int32_t* idx, const float* y, int64_t B, int32_t F, float* E,
+                              float* w, float* w0, float* P, int64_t features_M, int32_t k,
+                              float lr, int32_t optimizer, float keep_afm, uint64_t seed,
+                              float* const* acc, void* workspace, size_t ws_bytes, float* loss,
+                              void* stream);
+int hhfm_afm_noatt_train_det_scratch(int64_t B, int32_t F, int32_t k, int64_t features_M,
+                                     size_t* bytes);
+int hhfm_afm_noatt_train_step_det(const int32_t* idx, const float* y, int64_t B, int32_t F,
+                                  float* E, float* w, float* w0, float* P, int64_t features_M,
+                                  int32_t k, float lr, int32_t optimizer, float keep_afm,
+                                  uint64_t seed, float* const* acc, void* workspace,
+                                  size_t ws_bytes, void* scratch, size_t scratch_bytes,
+                                  float* loss, void* stream);
+
+/* ------------------------------------------------------------------------
  * H6 — one training step (`partial_fit`, sess.run((loss, optimizer))).
  *   FM   (FM.py:123-136):        loss = Σ (y − out)²/2 + λ·Σ E²/2
  *   HHFM (OurModel7.py:172-193): loss = −Σ log σ(pos − max_j neg_j) + λ·Σ E²/2

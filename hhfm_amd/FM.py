@@ -54,6 +54,8 @@ def parse_args(dataname, factor, TopK, argv=None):
     p.add_argument("--result_file", default="../result.txt")
     p.add_argument("--deterministic", type=int, default=0,
                    help="1: bit-reproducible training steps (row-ordered sums)")
+    p.add_argument("--filter_seen", type=int, default=0, choices=(0, 1),
+                   help="1: HR / NDCG / PRE over top-K lists without each key's train positives")
     return p.parse_args(argv)
 
 
@@ -123,17 +125,22 @@ class FM(ScoringModel):
         w0 = W["bias"] + (W["bn_beta"] - W["bn_moving_mean"] * a).sum()
         return self._np_out(ops.fm_score_rows(idx, self.table, w, float(w0), scale=a))
 
-    def catalog_topk(self, q, begin, count, K):
+    def catalog_topk(self, q, begin, count, K, exclude=None):
         """Top-K of items [begin, begin+count) by (u+f)·(i+f) + w_i (FM.py:172-185)
-        -> (scores, global item offsets) device tensors [B, K]."""
+        -> (scores, global item offsets) device tensors [B, K].  ``exclude``: an
+        ops.ExclusionLists, or a positive_feedback-style dict key tuple -> set of
+        table row ids (keys from ``q`` as harness.row_keys takes them): the top K
+        of each query's other items."""
         ncols = q.shape[1]
+        extra = {} if exclude is None else {"exclude": self._exclusion(q, exclude)}
         return ops.catalog_topk(q, self.table, ops.MODE_FM, int(K), self.n_user + begin, count,
                                 begin, self.weights["feature_bias"].reshape(-1), 0,
-                                (2, ncols) if ncols > 2 else (0, 0), (0, 0))
+                                (2, ncols) if ncols > 2 else (0, 0), (0, 0), **extra)
 
-    def topk(self, A, tp):
-        """Top-``tp`` item offsets in [0, n_item) by (u+f)·(i+f) + w_i."""
-        _, ids = self.catalog_topk(self._idx(A), 0, self.n_item, tp)
+    def topk(self, A, tp, exclude=None):
+        """Top-``tp`` item offsets in [0, n_item) by (u+f)·(i+f) + w_i; ``exclude``
+        as in :meth:`catalog_topk`."""
+        _, ids = self.catalog_topk(self._idx(A), 0, self.n_item, tp, exclude=exclude)
         return ids.cpu().numpy()
 
     def _run_fetch(self, fetch, feed):

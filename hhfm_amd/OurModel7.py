@@ -79,6 +79,8 @@ def parse_args(dataname, factor, Topk, argv=None):
     p.add_argument("--result_file", default="../result.txt")
     p.add_argument("--deterministic", type=int, default=0,
                    help="1: bit-reproducible training steps (row-ordered sums)")
+    p.add_argument("--filter_seen", type=int, default=0, choices=(0, 1),
+                   help="1: HR / NDCG / PRE over top-K lists without each key's train positives")
     p.add_argument("--pooling", default=None,
                    help="max | mean | sum, or ctx,time,final (default: the module's "
                         "Pooling1C / Pooling1T / Pooling1F)")
@@ -171,16 +173,28 @@ class OUR(ScoringModel):
                                     pooling2=self.pooling2)
         return self._np_out(out)
 
-    def catalog_topk(self, q, begin, count, K):
+    def catalog_topk(self, q, begin, count, K, exclude=None):
         """Top-K of items [begin, begin+count) by h·item (OurModel7.py:229-295)
-        -> (scores, global item offsets) device tensors [B, K]."""
+        -> (scores, global item offsets) device tensors [B, K].  ``exclude``: an
+        ops.ExclusionLists, or a positive_feedback-style dict key tuple -> set of
+        table row ids (keys from ``q`` as harness.row_keys takes them): the top K
+        of each query's other items; the two-way model has no such form."""
+        extra = {}
+        if exclude is not None:
+            if self.two_way:
+                raise NotImplementedError("OUR(two_way=True) has no catalog top-K with "
+                                          "exclusion lists")
+            extra["exclude"] = self._exclusion(q, exclude)
         ctx, tim = self._ranges(q.shape[1])
         return ops.catalog_topk(q, self.table, ops.MODE_HHFM, int(K), self.n_user + begin,
                                 count, begin, None, 0, ctx, tim, pooling=self.pooling,
-                                pooling2=self.pooling2)
+                                pooling2=self.pooling2, **extra)
 
-    def topk(self, A, tp):
-        _, ids = self.catalog_topk(self._idx(A), 0, self.n_item, tp)
+    def topk(self, A, tp, exclude=None):
+        if exclude is not None and self.two_way:   # before anything runs
+            raise NotImplementedError("OUR(two_way=True) has no catalog top-K with "
+                                      "exclusion lists")
+        _, ids = self.catalog_topk(self._idx(A), 0, self.n_item, tp, exclude=exclude)
         return ids.cpu().numpy()
 
     def _run_fetch(self, fetch, feed):

@@ -105,6 +105,20 @@ class ScoringModel(object):
             ops.validate_ids(t, self.features_M)
         return t
 
+    def _exclusion(self, A, exclude):
+        """``exclude`` of a topk call as ops.ExclusionLists (or None): the lists
+        themselves, or a positive_feedback-style dict key tuple -> set of table
+        row ids, its keys taken from the rows ``A`` as harness.row_keys does
+        (every column but the item, column 1)."""
+        if exclude is None or isinstance(exclude, ops.ExclusionLists):
+            return exclude
+        if not isinstance(exclude, dict):
+            raise TypeError("exclude must be an ops.ExclusionLists or a dict key -> set of ids")
+        rows = A.cpu().numpy() if isinstance(A, torch.Tensor) else np.asarray(A)
+        cols = [c for c in range(rows.shape[1]) if c != 1]
+        keys = [tuple(r) for r in rows[:, cols].tolist()]
+        return ops.exclusion_lists([exclude.get(key, ()) for key in keys], self.device)
+
     @property
     def table(self) -> torch.Tensor:
         """The embedding table in its storage dtype (what the kernels read)."""

@@ -26,6 +26,7 @@
 #include "hhfm_feature.h"
 
 #include <algorithm>
+#include <cfloat>
 #include <type_traits>
 
 namespace hhfm {
@@ -223,13 +224,25 @@ HHFM_DEV void insert_one(float* ls, int32_t* li, float s, int32_t it, int K) {
 // [B][ostride_b] column = tile (the threshold seed: the K-th largest of K
 // disjoint tiles' maxima is a score at least K items reach).  Selecting
 // layout, so every maximum is bit for bit a score the main pass computes.
-template <bool BF16, int KT, int KPAD, bool FM, bool SPLIT, bool STORE = false, bool GMAX = false>
+// EXCL (the selecting form only; include/hhfm.h "Exclusion lists"): a score
+// that passes the threshold is dropped when its item's table row is in the
+// query's list excl_rows[excl_ptr[q] .. excl_ptr[q + 1]) before the survivors
+// are counted — the lists, the per-split K-th score and the atomicMax hint
+// then see admissible items only.  The list is ascending and so are a split's
+// tiles: a lane keeps a cursor at its query's first entry not behind the
+// current tile, and that entry's value in a register, so a tile that holds no
+// excluded row of the wave's queries costs one compare.
+template <bool BF16, int KT, int KPAD, bool FM, bool SPLIT, bool STORE = false, bool GMAX = false,
+          bool EXCL = false>
 __global__ __launch_bounds__(256) void catalog_main(
     const float* __restrict__ H, const float* __restrict__ cst, int64_t B,
     const char* __restrict__ E, int64_t item_row_begin, int32_t N,
     const float* __restrict__ w, int K, int S, int tiles_per_split, int nqb,
     float* __restrict__ out_s, int32_t* __restrict__ out_i, int64_t ostride_b,
-    int64_t ostride_s, int32_t gbase, int32_t* __restrict__ gthr) {
+    int64_t ostride_s, int32_t gbase, int32_t* __restrict__ gthr,
+    const int64_t* __restrict__ excl_ptr = nullptr,
+    const int32_t* __restrict__ excl_rows = nullptr) {
+  static_assert(!EXCL || (!STORE && !GMAX), "exclusion lists filter the selecting form");
   constexpr int k = BF16 ? KT * 16 : KT * 8;   // factors
   constexpr int64_t ROWB = (int64_t)KT * 32;   // bytes per embedding row
   constexpr int EPC = BF16 ? 8 : 4;            // k-elements per 16-B chunk
@@ -299,6 +312,26 @@ __global__ __launch_bounds__(256) void catalog_main(
   float cq = 0.f;
   if constexpr (FM) cq = cst[q];
   float thr = (q < B) ? kNegInf : __builtin_huge_valf();
+  // this lane's query's list xr[0 .. xn), ascending table rows; xc: the first
+  // entry at or past the split's first row, xnext its value
+  const int32_t* xr = nullptr;
+  int64_t xn = 0, xc = 0;
+  int32_t xnext = kNoIdx;
+  if constexpr (EXCL) {
+    if (q < B && excl_rows) {
+      const int64_t x0 = excl_ptr[q];
+      xr = excl_rows + x0;
+      xn = excl_ptr[q + 1] - x0;
+      const int64_t first = item_row_begin + (int64_t)tb0 * kTile;
+      int64_t e = xn;
+      while (xc < e) {
+        const int64_t mid = (xc + e) >> 1;
+        if (xr[mid] < first) xc = mid + 1;
+        else e = mid;
+      }
+      if (xc < xn) xnext = xr[xc];
+    }
+  }
 
   // A operand: a ring of PF item tiles in flight (item row tile*32 + j, 16 B
   // per k-chunk); tile t is consumed from ring slot t % PF and its slot is
@@ -464,6 +497,34 @@ __global__ __launch_bounds__(256) void catalog_main(
 #pragma unroll
     for (int r = 0; r < 16; ++r) count += __popcll(pm[r]);
     if (count == 0) return;
+    if constexpr (EXCL) {
+      const int64_t base = item_row_begin + ibase;   // table row of the tile's first item
+      while (xc < xn && xnext < base) {              // (tiles without survivors are skipped)
+        ++xc;
+        xnext = xc < xn ? xr[xc] : kNoIdx;
+      }
+      if (__ballot(xc < xn && xnext < base + kTile)) {
+        // some query of the wave excludes an item of this tile: em = this
+        // lane's query's excluded rows of the tile; a lane whose score passed
+        // clears its bit, and the survivors are counted again
+        uint32_t em = 0;
+        int64_t c = xc;
+        int64_t v = xnext;
+        while (c < xn && v < base + kTile) {
+          em |= 1u << (int)(v - base);
+          ++c;
+          v = c < xn ? xr[c] : kNoIdx;
+        }
+        count = 0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+          pm[r] = __ballot(((pm[r] >> l) & 1) != 0 && ((em >> row) & 1) == 0);
+          count += __popcll(pm[r]);
+        }
+        if (count == 0) return;
+      }
+    }
     const uint64_t lbit = 1ull << l;
 #define HHFM_PASS(r) ((pm[r] & lbit) != 0)
 #define HHFM_PASSMASK(r) (pm[r])
@@ -1037,6 +1098,31 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// 4. exclusion lists on materialised scores
+// ---------------------------------------------------------------------------
+// One wave per query, one lane per list entry at a time: the entry's table
+// row, when it lies in [item_row_begin, item_row_begin + n), sends -FLT_MAX to
+// sc[b][(row - item_row_begin) >> shift].  shift 0: the score matrix of the
+// dense route (a masked item then ranks below every admissible one); shift 5:
+// the threshold seed's tile maxima (a tile that holds an excluded row leaves
+// the seed, so the K-th largest remaining maximum is reached by K admissible
+// items).  Rows outside the range — bad ids among them — are only compared.
+__global__ __launch_bounds__(256) void excl_mask_kernel(
+    const int64_t* __restrict__ excl_ptr, const int32_t* __restrict__ excl_rows, int64_t B,
+    int64_t item_row_begin, int32_t n, int shift, float* __restrict__ sc, int64_t ld) {
+  const int l = lane_id();
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  for (int64_t b = wave; b < B; b += nwave) {
+    const int64_t x1 = excl_ptr[b + 1];
+    for (int64_t x = excl_ptr[b] + l; x < x1; x += kWave) {
+      const int64_t off = (int64_t)excl_rows[x] - item_row_begin;
+      if (off >= 0 && off < n) sc[b * ld + (off >> shift)] = -FLT_MAX;
+    }
+  }
+}
+
 }  // namespace hhfm
 
 #include "catalog_fused.h"
@@ -1178,21 +1264,31 @@ static Plan make_plan(int64_t B, int32_t N, int32_t k, int32_t K, int32_t plan, 
   return p;
 }
 
-template <bool BF16, int KT, int KPAD, bool FM>
+// caller's exclusion lists (include/hhfm.h "Exclusion lists"); max_excl is
+// checked on the host and sizes nothing
+struct ExclLists {
+  const int64_t* ptr;
+  const int32_t* rows;
+  int64_t max_excl;
+};
+
+template <bool BF16, int KT, int KPAD, bool FM, bool EXCL = false>
 static void launch_main(const Plan& p, const float* H, const float* cst, int64_t B,
                         const char* E, int64_t item_row_begin, int32_t N,
                         const float* w, int K, float* os, int32_t* oi,
                         int64_t sb, int64_t ss, int32_t gbase, int32_t* gthr,
-                        int32_t plan, hipStream_t st) {
+                        int32_t plan, hipStream_t st, const ExclLists* x = nullptr) {
   constexpr bool kCanSplit = BF16 || KT >= 2;   // fp32 split steps pair two chunks
+  const int64_t* xp = EXCL ? x->ptr : nullptr;
+  const int32_t* xr = EXCL ? x->rows : nullptr;
   if (kCanSplit && !(plan & HHFM_PLAN_EXACT_FP32))
-    hipLaunchKernelGGL((catalog_main<BF16, KT, KPAD, FM, kCanSplit>), dim3(p.nqb * p.S),
-                       dim3(256), 0, st, H, cst, B, E, item_row_begin, N, w, K,
-                       p.S, p.tiles_per_split, p.nqb, os, oi, sb, ss, gbase, gthr);
+    hipLaunchKernelGGL((catalog_main<BF16, KT, KPAD, FM, kCanSplit, false, false, EXCL>),
+                       dim3(p.nqb * p.S), dim3(256), 0, st, H, cst, B, E, item_row_begin, N, w, K,
+                       p.S, p.tiles_per_split, p.nqb, os, oi, sb, ss, gbase, gthr, xp, xr);
   else
-    hipLaunchKernelGGL((catalog_main<BF16, KT, KPAD, FM, false>), dim3(p.nqb * p.S),
-                       dim3(256), 0, st, H, cst, B, E, item_row_begin, N, w, K,
-                       p.S, p.tiles_per_split, p.nqb, os, oi, sb, ss, gbase, gthr);
+    hipLaunchKernelGGL((catalog_main<BF16, KT, KPAD, FM, false, false, false, EXCL>),
+                       dim3(p.nqb * p.S), dim3(256), 0, st, H, cst, B, E, item_row_begin, N, w, K,
+                       p.S, p.tiles_per_split, p.nqb, os, oi, sb, ss, gbase, gthr, xp, xr);
 }
 
 // catalog_ring (K <= 32, bf16 k >= 128 / fp32 k >= 64, split-bf16 MFMA):
@@ -1263,17 +1359,18 @@ static bool dispatch_ring_gmax(int KT, const Plan& p, const float* H, const floa
   return true;
 }
 
-template <bool BF16, int KPAD, bool FM>
+template <bool BF16, int KPAD, bool FM, bool EXCL = false>
 static bool dispatch_kt(int KT, const Plan& p, const float* H, const float* cst,
                         int64_t B, const char* E, int64_t irb, int32_t N,
                         const float* w, int K, float* os, int32_t* oi, int64_t sb,
-                        int64_t ss, int32_t gbase, int32_t* gthr, int32_t plan, hipStream_t st) {
+                        int64_t ss, int32_t gbase, int32_t* gthr, int32_t plan, hipStream_t st,
+                        const ExclLists* x = nullptr) {
   switch (KT) {
-    case 1: launch_main<BF16, 1, KPAD, FM>(p, H, cst, B, E, irb, N, w, K, os, oi, sb, ss, gbase, gthr, plan, st); break;
-    case 2: launch_main<BF16, 2, KPAD, FM>(p, H, cst, B, E, irb, N, w, K, os, oi, sb, ss, gbase, gthr, plan, st); break;
-    case 4: launch_main<BF16, 4, KPAD, FM>(p, H, cst, B, E, irb, N, w, K, os, oi, sb, ss, gbase, gthr, plan, st); break;
-    case 8: launch_main<BF16, 8, KPAD, FM>(p, H, cst, B, E, irb, N, w, K, os, oi, sb, ss, gbase, gthr, plan, st); break;
-    case 16: launch_main<BF16, 16, KPAD, FM>(p, H, cst, B, E, irb, N, w, K, os, oi, sb, ss, gbase, gthr, plan, st); break;
+    case 1: launch_main<BF16, 1, KPAD, FM, EXCL>(p, H, cst, B, E, irb, N, w, K, os, oi, sb, ss, gbase, gthr, plan, st, x); break;
+    case 2: launch_main<BF16, 2, KPAD, FM, EXCL>(p, H, cst, B, E, irb, N, w, K, os, oi, sb, ss, gbase, gthr, plan, st, x); break;
+    case 4: launch_main<BF16, 4, KPAD, FM, EXCL>(p, H, cst, B, E, irb, N, w, K, os, oi, sb, ss, gbase, gthr, plan, st, x); break;
+    case 8: launch_main<BF16, 8, KPAD, FM, EXCL>(p, H, cst, B, E, irb, N, w, K, os, oi, sb, ss, gbase, gthr, plan, st, x); break;
+    case 16: launch_main<BF16, 16, KPAD, FM, EXCL>(p, H, cst, B, E, irb, N, w, K, os, oi, sb, ss, gbase, gthr, plan, st, x); break;
     default: return false;
   }
   return true;
@@ -1415,6 +1512,15 @@ static bool dispatch_store(int KT, int64_t B, int nqb, int32_t N, const float* H
   return true;
 }
 
+static void launch_excl_mask(const ExclLists& x, int64_t B, int64_t irb, int32_t n, int shift,
+                             float* sc, int64_t ld, hipStream_t st) {
+  if (!x.rows) return;   // no rows: every list is empty
+  int64_t blocks = (B + 3) / 4;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(excl_mask_kernel, dim3((int)blocks), dim3(256), 0, st, x.ptr, x.rows, B, irb,
+                     n, shift, sc, ld);
+}
+
 static void launch_merge(const float* in_s, const int32_t* in_i, int R, int64_t B,
                          int K, int64_t stride_r, int64_t stride_b, float* os,
                          int32_t* oi, hipStream_t st) {
@@ -1469,7 +1575,8 @@ static int catalog_topk_impl(
     int32_t global_item_base, int32_t K, float* top_score, int32_t* top_idx,
     void* workspace, size_t ws_bytes, int32_t plan, int32_t pooling, int32_t* status,
     void* stream, bool two_way = false, int32_t pooling2 = 0,
-    const Cars2Query* cars2 = nullptr, const NoAttQuery* noatt = nullptr) {
+    const Cars2Query* cars2 = nullptr, const NoAttQuery* noatt = nullptr,
+    const ExclLists* excl = nullptr) {
   PoolModes pm;
   PoolModes2 pm2{};
   if (!pooling_unpack(pooling, pm)) return HHFM_EINVAL;
@@ -1493,6 +1600,9 @@ static int catalog_topk_impl(
     return HHFM_EINVAL;
   if (K < 1 || K > item_count) return HHFM_EINVAL;
   if (K > 64) return HHFM_EUNSUPPORTED;
+  // exclusion lists: K admissible items must remain whatever the lists hold
+  if (excl && (excl->max_excl < 0 || (int64_t)K + excl->max_excl > item_count)) return HHFM_EINVAL;
+  if (excl && B > 0 && !excl->ptr) return HHFM_EINVAL;
   const bool bf16 = dtype == HHFM_BF16;
   const int epc2 = bf16 ? 16 : 8;  // k per 16-B chunk pair (two lane halves)
   if (k % epc2) return HHFM_EUNSUPPORTED;
@@ -1523,7 +1633,8 @@ static int catalog_topk_impl(
   // (two-way has no form of the fused kernel: it always forms H with
   // catalog_queries over TwoWayFeature and runs the main kernels below)
   const bool fused_size = item_count <= 8192 || (plan & HHFM_PLAN_FUSED);
-  if (!two_way && !cars2 && !noatt && p.dense && fused_size && K <= 32 && KT <= 8 && p.fS <= kFusedMaxS &&
+  // (nor has the fused kernel an exclusion form: lists take the score matrix)
+  if (!two_way && !cars2 && !noatt && !excl && p.dense && fused_size && K <= 32 && KT <= 8 && p.fS <= kFusedMaxS &&
       (B + kQPerWave - 1) / kQPerWave <= kFusedMaxGroups &&
       ctx_end - ctx_begin <= kFusedMaxCtx && time_end - time_begin <= kFusedMaxCtx &&
       !(plan & (HHFM_PLAN_GEMM | HHFM_PLAN_STORE))) {
@@ -1582,6 +1693,7 @@ static int catalog_topk_impl(
       else ok = fmm ? dispatch_store<false, true>(KT, B, p.nqb, item_count, H, cst, Eb, item_row_begin, wv, sc, p.ldsc, gthr, plan, st)
                     : dispatch_store<false, false>(KT, B, p.nqb, item_count, H, cst, Eb, item_row_begin, wv, sc, p.ldsc, gthr, plan, st);
       if (ok) {
+        if (excl) launch_excl_mask(*excl, B, item_row_begin, item_count, 0, sc, p.ldsc, st);
         launch_topk_dense(sc, B, item_count, p.ldsc, K, global_item_base, top_score, top_idx, st,
                           one);
         return (int)hipGetLastError();
@@ -1602,6 +1714,7 @@ static int catalog_topk_impl(
     g.C = sc;
     g.ldc = p.ldsc;
     launch_gemm(g, false, 0, st);
+    if (excl) launch_excl_mask(*excl, B, item_row_begin, item_count, 0, sc, p.ldsc, st);
     launch_topk_dense(sc, B, item_count, p.ldsc, K, global_item_base, top_score, top_idx, st, one);
     return (int)hipGetLastError();
   }
@@ -1613,7 +1726,8 @@ static int catalog_topk_impl(
     if (me != hipSuccess) return (int)me;
   }
   // (bf16 k = 256 would spill at two waves per SIMD: catalog_main keeps it)
-  const bool ring = K <= 32 && p.seed_n > 0 && (bf16 ? KT == 8 : (KT == 8 || KT == 16)) &&
+  // (nor with exclusion lists: catalog_ring has no EXCL form)
+  const bool ring = K <= 32 && p.seed_n > 0 && (bf16 ? KT == 8 : (KT == 8 || KT == 16)) && !excl &&
                     !(plan & (HHFM_PLAN_EXACT_FP32 | HHFM_PLAN_NO_RING));
   const int S_used = ring ? p.rS[ring_waves(bf16, plan) == 8 ? 1 : 0] : p.S;
   float* os;
@@ -1654,11 +1768,21 @@ static int catalog_topk_impl(
               : dispatch_gmax<false, false>(KT, B, p.nqb, p.seed_n, H, cst, Eb, irb, wv, ssc, G, plan, st);
     }
     if (!ok) return HHFM_EUNSUPPORTED;
+    // a seed tile that holds an excluded row of the query leaves its seed
+    if (excl) launch_excl_mask(*excl, B, irb, p.seed_n, 5, ssc, G, st);
     // gthr[b] = key of the K-th largest tile maximum
     launch_topk_dense(ssc, B, G, G, K, 0, sds, sdi, st, false, gthr);
   }
 #define HHFM_MAIN_ARGS KT, p, H, cst, B, Eb, (int64_t)item_row_begin, item_count, w, K, os, oi, sb, ss, gbase, gthr, plan, st
-  if (ring) {
+  if (excl) {   // catalog_main's EXCL form (selection over admissible items only)
+    if (K <= 32) {
+      if (bf16) ok = fm ? dispatch_kt<true, 32, true, true>(HHFM_MAIN_ARGS, excl) : dispatch_kt<true, 32, false, true>(HHFM_MAIN_ARGS, excl);
+      else ok = fm ? dispatch_kt<false, 32, true, true>(HHFM_MAIN_ARGS, excl) : dispatch_kt<false, 32, false, true>(HHFM_MAIN_ARGS, excl);
+    } else {
+      if (bf16) ok = fm ? dispatch_kt<true, 64, true, true>(HHFM_MAIN_ARGS, excl) : dispatch_kt<true, 64, false, true>(HHFM_MAIN_ARGS, excl);
+      else ok = fm ? dispatch_kt<false, 64, true, true>(HHFM_MAIN_ARGS, excl) : dispatch_kt<false, 64, false, true>(HHFM_MAIN_ARGS, excl);
+    }
+  } else if (ring) {
     if (bf16) ok = fm ? dispatch_ring<true, true>(HHFM_MAIN_ARGS) : dispatch_ring<true, false>(HHFM_MAIN_ARGS);
     else ok = fm ? dispatch_ring<false, true>(HHFM_MAIN_ARGS) : dispatch_ring<false, false>(HHFM_MAIN_ARGS);
   } else if (K <= 32) {
@@ -1702,6 +1826,25 @@ extern "C" int hhfm_catalog_topk_pool(
                            time_end, E, features_M, k, dtype, w, item_row_begin, item_count,
                            global_item_base, K, top_score, top_idx, workspace, ws_bytes, plan,
                            pooling, status, stream);
+}
+
+// Exclusion lists (include/hhfm.h "Exclusion lists"): hhfm_catalog_topk_pool
+// over each query's admissible items.  The dense route masks the score matrix,
+// the streaming route runs catalog_main's EXCL form behind a seed whose tiles
+// with excluded rows are taken out; never the fused kernel or the ring.
+extern "C" int hhfm_catalog_topk_excl(
+    const int32_t* qidx, int64_t B, int32_t ncols, int32_t mode,
+    int32_t user_col, int32_t ctx_begin, int32_t ctx_end, int32_t time_begin,
+    int32_t time_end, const void* E, int64_t features_M, int32_t k,
+    int32_t dtype, const float* w, int32_t item_row_begin, int32_t item_count,
+    int32_t global_item_base, int32_t K, float* top_score, int32_t* top_idx,
+    void* workspace, size_t ws_bytes, int32_t plan, int32_t pooling, int32_t* status,
+    void* stream, const int64_t* excl_ptr, const int32_t* excl_rows, int64_t max_excl) {
+  const ExclLists x{excl_ptr, excl_rows, max_excl};
+  return catalog_topk_impl(qidx, B, ncols, mode, user_col, ctx_begin, ctx_end, time_begin,
+                           time_end, E, features_M, k, dtype, w, item_row_begin, item_count,
+                           global_item_base, K, top_score, top_idx, workspace, ws_bytes, plan,
+                           pooling, status, stream, false, 0, nullptr, nullptr, &x);
 }
 
 // Two-way: H from catalog_queries over TwoWayFeature, then the main kernels unchanged;

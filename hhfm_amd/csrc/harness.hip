@@ -19,6 +19,8 @@
 // the reference's float64 HR / NDCG / PRE values.
 #include "hhfm_common.h"
 
+#include <hipcub/hipcub.hpp>
+
 namespace hhfm {
 
 // row key (every column but item_col, in column order) vs keys[m]
@@ -89,6 +91,102 @@ __global__ __launch_bounds__(256) void topk_walk_kernel(
   }
 }
 
+// Exclusion lists (include/hhfm.h "Exclusion lists"): per row, the run of
+// `codes` that carries its key's rank — the key's items, ascending — is the
+// row's list.  pf_run finds the run codes[a .. e) of a row (empty for an
+// unknown key) and, under keep_own, the place `own` of the row's own item in
+// it (-1: not there), which the list leaves out.
+struct PfRun {
+  int64_t a, e, own;
+};
+
+HHFM_DEV PfRun pf_run(const int32_t* __restrict__ keys, int64_t nkeys, int key_cols,
+                      const int64_t* __restrict__ codes, int64_t ncodes, const int32_t* row,
+                      int ncols, int item_col, int keep_own) {
+  PfRun r{0, 0, -1};
+  int64_t lo = 0, hi = nkeys;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (key_cmp(row, ncols, item_col, keys + mid * key_cols) > 0) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo >= nkeys || key_cmp(row, ncols, item_col, keys + lo * key_cols) != 0) return r;
+  auto lower = [&](int64_t code) {
+    int64_t x = 0, y = ncodes;
+    while (x < y) {
+      const int64_t mid = (x + y) >> 1;
+      if (codes[mid] < code) x = mid + 1;
+      else y = mid;
+    }
+    return x;
+  };
+  r.a = lower(lo << 32);
+  r.e = lower((lo + 1) << 32);
+  if (keep_own) {
+    const int64_t code = (lo << 32) | (int64_t)(uint32_t)row[item_col];
+    const int64_t x = lower(code);
+    if (x < r.e && codes[x] == code) r.own = x;
+  }
+  return r;
+}
+
+// sizing: one thread per row, counts[b] = length of row b's list, counts[B] = 0
+__global__ __launch_bounds__(256) void pf_excl_count_kernel(
+    const int32_t* __restrict__ keys, int64_t nkeys, int key_cols,
+    const int64_t* __restrict__ codes, int64_t ncodes, const int32_t* __restrict__ rows,
+    int64_t B, int ncols, int item_col, int keep_own, int64_t* __restrict__ counts) {
+  for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b <= B;
+       b += (int64_t)gridDim.x * blockDim.x) {
+    if (b == B) {
+      counts[B] = 0;
+      break;
+    }
+    const PfRun r = pf_run(keys, nkeys, key_cols, codes, ncodes, rows + b * ncols, ncols,
+                           item_col, keep_own);
+    counts[b] = (r.e - r.a) - (r.own >= 0 ? 1 : 0);
+  }
+}
+
+// fill: one wave per row (every lane finds the same run, the copy is spread
+// over the lanes), out[ptr[b] ..] = the list (ptr = the scanned counts)
+__global__ __launch_bounds__(256) void pf_excl_fill_kernel(
+    const int32_t* __restrict__ keys, int64_t nkeys, int key_cols,
+    const int64_t* __restrict__ codes, int64_t ncodes, const int32_t* __restrict__ rows,
+    int64_t B, int ncols, int item_col, int keep_own, const int64_t* __restrict__ ptr,
+    int32_t* __restrict__ out) {
+  const int l = threadIdx.x & (kWave - 1);
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  for (int64_t b = wave; b < B; b += nwave) {
+    const PfRun r = pf_run(keys, nkeys, key_cols, codes, ncodes, rows + b * ncols, ncols,
+                           item_col, keep_own);
+    int32_t* dst = out + ptr[b];
+    const int64_t room = ptr[b + 1] - ptr[b];   // (a sizing call with other arguments: stay inside)
+    for (int64_t x = r.a + l; x < r.e; x += kWave) {
+      if (x == r.own) continue;
+      const int64_t at = (x - r.a) - (r.own >= 0 && x > r.own ? 1 : 0);
+      if (at < room) dst[at] = (int32_t)(uint32_t)codes[x];
+    }
+  }
+}
+
+// exclusive scan of n int64 values by one workgroup, chunk by chunk
+__global__ __launch_bounds__(1024) void scan_i64_kernel(const int64_t* __restrict__ in, int64_t n,
+                                                        int64_t* __restrict__ out) {
+  using Scan = hipcub::BlockScan<int64_t, 1024>;
+  __shared__ typename Scan::TempStorage tmp;
+  int64_t carry = 0;
+  for (int64_t base = 0; base < n; base += 1024) {
+    const int64_t x = base + threadIdx.x;
+    const int64_t v = x < n ? in[x] : 0;
+    int64_t ex, total;
+    Scan(tmp).ExclusiveSum(v, ex, total);
+    if (x < n) out[x] = carry + ex;
+    carry += total;
+    __syncthreads();   // tmp is reused by the next chunk
+  }
+}
+
 static unsigned grid_1d(int64_t n) {
   int64_t g = (n + 255) / 256;
   if (g > 16384) g = 16384;
@@ -112,6 +210,48 @@ extern "C" int hhfm_pf_contains(const int32_t* keys, int64_t nkeys, int32_t key_
   hipLaunchKernelGGL(pf_contains_kernel, dim3(grid_1d(B * num)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), keys, nkeys, key_cols, codes,
                      ncodes, rows, B, ncols, item_col, cand, num, out);
+  return (int)hipGetLastError();
+}
+
+// counts int64 [B + 1] (scanned into excl_ptr by the sizing call)
+extern "C" int hhfm_pf_exclusion_lists_workspace(int64_t B, size_t* ws_bytes) {
+  if (!ws_bytes || B < 0) return HHFM_EINVAL;
+  *ws_bytes = (((size_t)B + 1) * sizeof(int64_t) + 255) & ~size_t(255);
+  return HHFM_OK;
+}
+
+extern "C" int hhfm_pf_exclusion_lists(const int32_t* keys, int64_t nkeys, int32_t key_cols,
+                                       const int64_t* codes, int64_t ncodes,
+                                       const int32_t* rows, int64_t B, int32_t ncols,
+                                       int32_t item_col, int32_t keep_own, int64_t* excl_ptr,
+                                       int32_t* excl_rows, int64_t capacity, void* workspace,
+                                       size_t ws_bytes, void* stream) {
+  if (B < 0 || nkeys < 0 || ncodes < 0 || ncols < 2 || ncols > 64) return HHFM_EINVAL;
+  if (item_col < 0 || item_col >= ncols || key_cols != ncols - 1) return HHFM_EINVAL;
+  if (!excl_ptr || (B && !rows) || (nkeys && !keys) || (ncodes && !codes)) return HHFM_EINVAL;
+  if (excl_rows && capacity < 0) return HHFM_EINVAL;
+  size_t need = 0;
+  hhfm_pf_exclusion_lists_workspace(B, &need);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!excl_rows) {   // sizing call: per-row counts, then their exclusive scan
+    if (!workspace || ws_bytes < need) return HHFM_EWORKSPACE;
+    int64_t* counts = reinterpret_cast<int64_t*>(workspace);
+    hipLaunchKernelGGL(pf_excl_count_kernel, dim3(grid_1d(B + 1)), dim3(256), 0, st, keys, nkeys,
+                       key_cols, codes, ncodes, rows, B, ncols, item_col, keep_own, counts);
+    hipLaunchKernelGGL(scan_i64_kernel, dim3(1), dim3(1024), 0, st, counts, B + 1, excl_ptr);
+    return (int)hipGetLastError();
+  }
+  // fill call: excl_ptr is the sizing call's; its total against the capacity
+  int64_t total = 0;
+  hipError_t e = hipMemcpyAsync(&total, excl_ptr + B, sizeof(total), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return (int)e;
+  if (total < 0) return HHFM_EINVAL;
+  if (capacity < total) return HHFM_EWORKSPACE;
+  if (B == 0 || total == 0) return HHFM_OK;
+  hipLaunchKernelGGL(pf_excl_fill_kernel, dim3(grid_1d(B * kWave)), dim3(256), 0, st, keys, nkeys,
+                     key_cols, codes, ncodes, rows, B, ncols, item_col, keep_own, excl_ptr,
+                     excl_rows);
   return (int)hipGetLastError();
 }
 

@@ -145,6 +145,49 @@ PYBIND11_MODULE(_hhfm, m) {
           check(rc, "hhfm_catalog_topk_pool");
         });
 
+  // exclusion lists (include/hhfm.h "Exclusion lists")
+  m.def("catalog_topk_excl",
+        [](uptr qidx, int64_t B, int ncols, int mode, int ucol, int c0, int c1,
+           int t0, int t1, uptr E, int64_t M, int k, int dtype, uptr w,
+           int item_row_begin, int item_count, int global_item_base, int K,
+           uptr top_score, uptr top_idx, uptr ws, size_t ws_bytes, int plan, int pooling,
+           uptr status, uptr stream, uptr excl_ptr, uptr excl_rows, int64_t max_excl) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_catalog_topk_excl(
+                P<const int32_t>(qidx), B, ncols, mode, ucol, c0, c1, t0, t1,
+                P<const void>(E), M, k, dtype, P<const float>(w),
+                item_row_begin, item_count, global_item_base, K,
+                P<float>(top_score), P<int32_t>(top_idx), P<void>(ws), ws_bytes, plan,
+                pooling, P<int32_t>(status), P<void>(stream), P<const int64_t>(excl_ptr),
+                P<const int32_t>(excl_rows), max_excl);
+          }
+          check(rc, "hhfm_catalog_topk_excl");
+        });
+
+  m.def("pf_exclusion_lists_workspace", [](int64_t B) {
+    size_t n = 0;
+    check(hhfm_pf_exclusion_lists_workspace(B, &n), "hhfm_pf_exclusion_lists_workspace");
+    return n;
+  });
+
+  m.def("pf_exclusion_lists",
+        [](uptr keys, int64_t nkeys, int key_cols, uptr codes, int64_t ncodes, uptr rows,
+           int64_t B, int ncols, int item_col, int keep_own, uptr excl_ptr, uptr excl_rows,
+           int64_t capacity, uptr ws, size_t ws_bytes, uptr stream) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_pf_exclusion_lists(P<const int32_t>(keys), nkeys, key_cols,
+                                         P<const int64_t>(codes), ncodes, P<const int32_t>(rows),
+                                         B, ncols, item_col, keep_own, P<int64_t>(excl_ptr),
+                                         P<int32_t>(excl_rows), capacity, P<void>(ws), ws_bytes,
+                                         P<void>(stream));
+          }
+          check(rc, "hhfm_pf_exclusion_lists");
+        });
+
   // the two-way entry points (include/hhfm.h "Two-way pooling")
   m.def("hybrid_score_rows_pool2",
         [](uptr idx, int64_t B, int ncols, int ucol, int icol, int c0, int c1,

@@ -289,6 +289,41 @@ class Train(object):
                         n = n + 1
         return [np.average(hits), np.average(ndcg), np.average(pre)]
 
+    def evaluate_TopK_filtered(self, data1):
+        """evaluate_TopK over top-K lists that leave out the train positives of
+        each row's key — what the reference's walk tries at FM.py:354-355, where
+        it tests the target instead of the prediction.  The same
+        ``np.random.randint`` batches; the lists come from positive_feedback with
+        the row's own item kept in play (keep_own: a target that is a train
+        positive of its key must stay reachable); the walk is the plain one: the
+        hit rank is the target's place among the first TopK predictions, no skip
+        rule, no row leaves the denominator.  Needs a model on the GPU."""
+        from . import ops
+        size = np.min([3000, len(data1)])
+        hits, ndcg, pre = [], [], []
+        dat = data1.values
+        num = self.eval_num
+        dev = self._device()
+        if dev is None:
+            raise NotImplementedError("evaluate_TopK_filtered needs a model on the GPU")
+        import torch
+        for _ in range(int(size / num)):
+            feed = np.array(dat[:, 1:][np.random.randint(0, len(dat), num)], dtype=np.int64)
+            pairs = self._device_pairs(dev, feed.shape[1] - 1)
+            rows = torch.from_numpy(np.ascontiguousarray(feed, dtype=np.int32)).to(dev)
+            lists = ops.pf_exclusion_lists(pairs.keys, pairs.codes, rows, 1, keep_own=True)
+            prediction = np.asarray(self.model.topk(feed, 20, exclude=lists)) + self.n_user
+            for i, line in enumerate(feed):
+                at = np.flatnonzero(prediction[i][:self.TopK] == line[1])
+                if at.size:
+                    n = int(at[0])
+                    hits.append(1)
+                    ndcg.append(np.log(2) / np.log(n + 2))
+                    pre.append(1 / (n + 1))
+                else:
+                    hits.append(0); ndcg.append(0); pre.append(0)
+        return [np.average(hits), np.average(ndcg), np.average(pre)]
+
     def _device_walk(self, dev, feed, prediction):
         """hhfm_pf_contains (target test) + hhfm_topk_walk for one batch ->
         numpy int32 outcomes (see ops.topk_walk)."""

@@ -247,13 +247,16 @@ def catalog_topk(qidx: torch.Tensor, E: torch.Tensor, mode: int, K: int,
                  w: Optional[torch.Tensor] = None, user_col: int = 0,
                  ctx: Tuple[int, int] = (0, 0), time: Tuple[int, int] = (0, 0),
                  status: Optional[torch.Tensor] = None, plan: int = 0, pooling=None,
-                 pooling2=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                 pooling2=None, exclude: Optional["ExclusionLists"] = None
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Full-catalog score + top-K (FM.topk FM.py:172-198, OUR.topk
     OurModel7.py:229-307). Returns (scores float32 [B,K], ids int32 [B,K]).
     ``plan``: PLAN_* flags (PLAN_EXACT_FP32, _NO_SEED, _NO_RING, _RING_ALT,
     _GEMM, _ONE_WAVE).  ``pooling`` / ``pooling2``: as in
     :func:`hybrid_score_rows` (MODE_HHFM only; the two-way model never takes
-    the small-catalog fused kernel)."""
+    the small-catalog fused kernel).  ``exclude``: an :class:`ExclusionLists`
+    of table rows per query — the top K of the other items
+    (hhfm_catalog_topk_excl; not with ``pooling2``)."""
     _idx(qidx, "qidx")
     dev = _need_cuda(qidx, E, w)
     B, ncols = qidx.shape
@@ -265,6 +268,21 @@ def catalog_topk(qidx: torch.Tensor, E: torch.Tensor, mode: int, K: int,
     ws = _catalog_workspace(dev, st, nat.catalog_topk_workspace(B, item_count, k, K))
     top_s = torch.empty(B, K, dtype=torch.float32, device=dev)
     top_i = torch.empty(B, K, dtype=torch.int32, device=dev)
+    if exclude is not None:
+        if pooling2 is not None:
+            raise NotImplementedError("exclusion lists have no two-way form")
+        if exclude.ptr.numel() != B + 1:
+            raise ValueError(f"exclude holds {exclude.ptr.numel() - 1} lists for {B} queries")
+        _need_cuda(qidx, exclude.ptr, exclude.rows)
+        nat.catalog_topk_excl(qidx.data_ptr(), B, ncols, mode, user_col, ctx[0], ctx[1],
+                              time[0], time[1], E.data_ptr(), M, k, _dtype_code(E),
+                              0 if w is None else w.data_ptr(), item_row_begin, item_count,
+                              global_item_base, K, top_s.data_ptr(), top_i.data_ptr(),
+                              ws.data_ptr(), ws.numel(), int(plan), word,
+                              _status_ptr(status), st, exclude.ptr.data_ptr(),
+                              exclude.rows.data_ptr() if exclude.rows.numel() else 0,
+                              int(exclude.max_len))
+        return top_s, top_i
     if pooling2 is not None:
         nat.catalog_topk_pool2(qidx.data_ptr(), B, ncols, mode, user_col, ctx[0], ctx[1],
                                time[0], time[1], E.data_ptr(), M, k, _dtype_code(E),
@@ -670,6 +688,66 @@ def pf_contains(keys: torch.Tensor, codes: torch.Tensor, rows: torch.Tensor, ite
                          0 if cand is None else cand.data_ptr(), num, out.data_ptr(),
                          _stream(rows.device))
     return out if cand is not None else out[:, 0]
+
+
+class ExclusionLists:
+    """Per-query lists of table rows a catalog top-K leaves out (include/hhfm.h
+    "Exclusion lists"): ``ptr`` int64 [B + 1] and ``rows`` int32 [ptr[B]]
+    device tensors (ascending within a query), ``max_len`` the longest list."""
+
+    def __init__(self, ptr: torch.Tensor, rows: torch.Tensor, max_len: int):
+        if ptr.dtype != torch.int64 or rows.dtype != torch.int32:
+            raise TypeError("ptr int64, rows int32")
+        self.ptr = ptr
+        self.rows = rows
+        self.max_len = int(max_len)
+
+    def __len__(self):
+        return self.ptr.numel() - 1
+
+
+def pf_exclusion_lists(keys: torch.Tensor, codes: torch.Tensor, rows: torch.Tensor,
+                       item_col: int, keep_own: bool = False) -> ExclusionLists:
+    """The positive_feedback items of every row's key as :class:`ExclusionLists`
+    (hhfm_pf_exclusion_lists; keys / codes / rows as in :func:`pf_contains`).
+    ``keep_own`` leaves a row's own item out of its list.  Two calls — sizes,
+    then the lists; the read of ``ptr[B]`` in between synchronises."""
+    dev = _need_cuda(keys, codes, rows)
+    if keys.dtype != torch.int32 or codes.dtype != torch.int64 or rows.dtype != torch.int32:
+        raise TypeError("keys int32, codes int64, rows int32")
+    B, ncols = rows.shape
+    nat = native()
+    st = _stream(dev)
+    ws = _workspace(dev, nat.pf_exclusion_lists_workspace(B))
+    ptr = torch.empty(B + 1, dtype=torch.int64, device=dev)
+    args = (keys.data_ptr() if keys.numel() else 0, keys.shape[0], ncols - 1,
+            codes.data_ptr() if codes.numel() else 0, codes.numel(),
+            rows.data_ptr() if B else 0, B, ncols, item_col, int(bool(keep_own)), ptr.data_ptr())
+    nat.pf_exclusion_lists(*args, 0, 0, ws.data_ptr(), ws.numel(), st)
+    host = ptr.cpu()
+    total = int(host[B])
+    out = torch.empty(total, dtype=torch.int32, device=dev)
+    if total:
+        nat.pf_exclusion_lists(*args, out.data_ptr(), total, ws.data_ptr(), ws.numel(), st)
+    max_len = int((host[1:] - host[:-1]).max()) if B else 0
+    return ExclusionLists(ptr, out, max_len)
+
+
+def exclusion_lists(seqs: Sequence, device) -> ExclusionLists:
+    """:class:`ExclusionLists` of B host sequences of table-row ids: each is
+    sorted, freed of duplicates and uploaded."""
+    import numpy as np
+    lists = [np.unique(np.asarray(list(s), dtype=np.int64)) for s in seqs]
+    ptr = np.zeros(len(lists) + 1, dtype=np.int64)
+    if lists:
+        np.cumsum([len(x) for x in lists], out=ptr[1:])
+    flat = np.concatenate(lists) if lists else np.zeros(0, np.int64)
+    if flat.size and (flat.min() < -2 ** 31 or flat.max() >= 2 ** 31):
+        raise ValueError("exclusion ids must fit int32")
+    dev = torch.device(device)
+    return ExclusionLists(torch.from_numpy(ptr).to(dev),
+                          torch.from_numpy(flat.astype(np.int32)).to(dev),
+                          max((len(x) for x in lists), default=0))
 
 
 def topk_walk(pred: torch.Tensor, target: torch.Tensor, positive: torch.Tensor,

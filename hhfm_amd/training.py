@@ -382,8 +382,10 @@ def _log(tr, line):
 
 
 def _evaluate(tr):
+    # --filter_seen 1: the top-K lists leave out each key's train positives
+    topk = tr.evaluate_TopK_filtered if getattr(tr.args, "filter_seen", 0) else tr.evaluate_TopK
     return (tr.evaluate_AUC(tr.data.Train_data), tr.evaluate_AUC(tr.data.Test_data),
-            tr.evaluate_TopK(tr.data.Test_data))
+            topk(tr.data.Test_data))
 
 
 def _report_init(tr):

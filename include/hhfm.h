@@ -354,6 +354,74 @@ int hhfm_catalog_topk_pool2(const int32_t* qidx, int64_t B, int32_t ncols,
                             int32_t pooling2, int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Exclusion lists — catalog top-K over the items a query has not seen yet
+ * (what evaluate_TopK's walk tries at FM.py:354-355, where it tests the target
+ * instead of the prediction: SURVEY §8a-H3).  Pure additions: every earlier
+ * entry point keeps its signature and behaviour, HHFM_ABI_VERSION stays 6.
+ *
+ * Lists (CSR over the B queries of one call, device memory):
+ *   excl_ptr   int64 [B + 1], excl_ptr[0] = 0, non-decreasing;
+ *   excl_rows  int32 [excl_ptr[B]]: TABLE ROW ids (rows of E: the ids the
+ *              loader assigns and `codes` below stores in its low word),
+ *              strictly ascending within a query.
+ * The ids do not depend on the item shard: a row outside [item_row_begin,
+ * item_row_begin + item_count) is ignored, and so is a negative or
+ * >= features_M id — ids are compared, never used as an index.
+ *
+ * hhfm_catalog_topk_excl takes hhfm_catalog_topk_pool's arguments, then
+ * excl_ptr, excl_rows, max_excl.  HHFM_MODE_FM with pooling 0 and
+ * HHFM_MODE_HHFM with any pooling word.  The result is the top K of the
+ * range's non-excluded items in the same (score desc, index asc) order, every
+ * score bit for bit the plain call's score of that item; with every list empty
+ * the output equals the plain call's.  max_excl is the caller's promise of the
+ * longest list: K + max_excl > item_count (or max_excl < 0) is HHFM_EINVAL
+ * before anything is launched, so no list can leave a range short of K items.
+ * A list longer than max_excl may leave that query's output unspecified; the
+ * kernels size and index nothing by max_excl.  excl_ptr NULL with B > 0 is
+ * HHFM_EINVAL; excl_rows NULL means every list is empty.  The workspace is
+ * hhfm_catalog_topk_workspace's, unchanged.
+ * Routes: the score matrix (HHFM_PLAN_GEMM: from the GEMM)
+ * with the excluded entries set to -FLT_MAX before the dense top-K, or the
+ * streaming kernel's exclusion form behind a threshold seed without the tiles
+ * that hold an excluded row.  The fused small-catalog kernel and the ring are
+ * never taken: HHFM_PLAN_FUSED, _STORE, _NO_RING and _RING_ALT are accepted
+ * without effect; _EXACT_FP32, _GEMM, _NO_SEED and _ONE_WAVE keep their meaning.
+ * Not built: exclusion forms of the two-way, CARS2, AFM (with or without
+ * attention) and DeepFM catalogs, of the ring and of the fused kernel, and
+ * lists that run a range short of K.
+ *
+ * hhfm_pf_exclusion_lists builds the lists of `rows` from positive_feedback's
+ * device arrays (keys / codes as for hhfm_pf_contains below; in `codes` the
+ * items of one key are one contiguous ascending run): row b's list is its
+ * key's run, empty for an unknown key; keep_own != 0 leaves the row's own
+ * item (column item_col) out, as a filtered evaluation must for its target.
+ * Two calls:
+ *   excl_rows == NULL  writes excl_ptr [B + 1] alone (per-row counts and their
+ *                      exclusive scan, on the stream; needs the workspace of
+ *                      hhfm_pf_exclusion_lists_workspace(B), a host-only query);
+ *   excl_rows != NULL  fills the lists for the excl_ptr of the first call (same
+ *                      arguments).  It reads excl_ptr[B] back (the stream is
+ *                      synchronised): capacity < excl_ptr[B] is
+ *                      HHFM_EWORKSPACE and nothing is written.
+ * ---------------------------------------------------------------------- */
+int hhfm_catalog_topk_excl(const int32_t* qidx, int64_t B, int32_t ncols,
+                           int32_t mode, int32_t user_col, int32_t ctx_begin,
+                           int32_t ctx_end, int32_t time_begin, int32_t time_end,
+                           const void* E, int64_t features_M, int32_t k,
+                           int32_t dtype, const float* w, int32_t item_row_begin,
+                           int32_t item_count, int32_t global_item_base, int32_t K,
+                           float* top_score, int32_t* top_idx, void* workspace,
+                           size_t ws_bytes, int32_t plan, int32_t pooling,
+                           int32_t* status, void* stream, const int64_t* excl_ptr,
+                           const int32_t* excl_rows, int64_t max_excl);
+int hhfm_pf_exclusion_lists_workspace(int64_t B, size_t* ws_bytes);
+int hhfm_pf_exclusion_lists(const int32_t* keys, int64_t nkeys, int32_t key_cols,
+                            const int64_t* codes, int64_t ncodes, const int32_t* rows,
+                            int64_t B, int32_t ncols, int32_t item_col, int32_t keep_own,
+                            int64_t* excl_ptr, int32_t* excl_rows, int64_t capacity,
+                            void* workspace, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Top-K merge of R sorted partial lists per query (the item-sharded
  * multi-GPU path: RCCL all-gather output, rank-major).  Replaces the single
  * tf.nn.top_k over the full catalog (FM.py:185, OurModel7.py:295).

@@ -1900,6 +1900,23 @@ extern "C" int hhfm_afm_noatt_catalog_topk(
                            nullptr, &nq);
 }
 
+// make_plan as numbers, for the host-side tests of the workspace layout
+// (tests/test_workspace_contract.py; not part of include/hhfm.h): out[0..9] =
+// off_H, off_cst, off_thr, off_ps, off_pi, off_sc, off_seed_sc, off_seed_s,
+// off_seed_i, total; out[10..15] = dense, fS, S, rS[0], rS[1], seed_n.
+extern "C" int hhfm_debug_catalog_plan(int64_t B, int32_t item_count, int32_t k, int32_t K,
+                                       int32_t plan, int32_t dtype, int64_t* out) {
+  if (!out || B < 1 || item_count < 1 || k < 1 || K < 1 || K > 64) return HHFM_EINVAL;
+  if (dtype != HHFM_F32 && dtype != HHFM_BF16) return HHFM_EINVAL;
+  const Plan p = make_plan(B, item_count, k, K, plan, dtype == HHFM_BF16);
+  const int64_t v[16] = {(int64_t)p.off_H, (int64_t)p.off_cst, (int64_t)p.off_thr,
+                         (int64_t)p.off_ps, (int64_t)p.off_pi, (int64_t)p.off_sc,
+                         (int64_t)p.off_seed_sc, (int64_t)p.off_seed_s, (int64_t)p.off_seed_i,
+                         (int64_t)p.total, p.dense, p.fS, p.S, p.rS[0], p.rS[1], p.seed_n};
+  for (int i = 0; i < 16; ++i) out[i] = v[i];
+  return HHFM_OK;
+}
+
 #if HHFM_FUSED_TIMING
 // diagnostic builds only: read and clear the fused kernel's per-workgroup
 // phase stamps (out: kFusedTimingWG x kFusedMarks)

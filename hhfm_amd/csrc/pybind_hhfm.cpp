@@ -14,6 +14,10 @@
 
 #include "hhfm.h"
 
+// catalog_topk.hip: make_plan as numbers (a test hook, not in include/hhfm.h)
+extern "C" int hhfm_debug_catalog_plan(int64_t B, int32_t item_count, int32_t k, int32_t K,
+                                       int32_t plan, int32_t dtype, int64_t* out);
+
 namespace py = pybind11;
 using uptr = std::uintptr_t;
 
@@ -34,6 +38,7 @@ static void check(int rc, const char* what) {
 PYBIND11_MODULE(_hhfm, m) {
   m.doc() = "pybind11 binding of libhhfm (MI355X FM-family scoring kernels)";
   m.attr("ABI_VERSION") = HHFM_ABI_VERSION;
+  m.attr("CATALOG_WS_ZERO") = (int64_t)HHFM_CATALOG_WS_ZERO;
   m.attr("F32") = (int)HHFM_F32;
   m.attr("BF16") = (int)HHFM_BF16;
   m.attr("MODE_FM") = (int)HHFM_MODE_FM;
@@ -324,6 +329,19 @@ PYBIND11_MODULE(_hhfm, m) {
           }
           check(rc, "hhfm_cars2_train_step");
         });
+
+  // the catalog workspace plan's region offsets and split counts (tests only)
+  m.def("debug_catalog_plan", [](int64_t B, int item_count, int k, int K, int plan, int dtype) {
+    std::vector<int64_t> v(16);
+    check(hhfm_debug_catalog_plan(B, item_count, k, K, plan, dtype, v.data()),
+          "hhfm_debug_catalog_plan");
+    static const char* names[16] = {"off_H", "off_cst", "off_thr", "off_ps", "off_pi", "off_sc",
+                                    "off_seed_sc", "off_seed_s", "off_seed_i", "total", "dense",
+                                    "fS", "S", "rS0", "rS1", "seed_n"};
+    py::dict d;
+    for (int i = 0; i < 16; ++i) d[names[i]] = v[i];
+    return d;
+  });
 
   m.def("catalog_topk_workspace",
         [](int64_t B, int item_count, int k, int K) {

@@ -298,6 +298,22 @@ int hhfm_hybrid_score_rows_pool2(const int32_t* idx, int64_t B, int32_t ncols,
  * before the first call (the small-catalog kernel's per-call arrival
  * counters: every call leaves them zero again); a buffer used by other
  * entry points in between must be re-zeroed there (ABI v6).
+ * What the tests pin (tests/test_gpu_workspace_contract.py, region by region
+ * in profiles/workspace_contract_map.txt):
+ *   - only that prefix must be zero: the rest of the workspace may hold
+ *     anything when a call starts (every region is written by the call before
+ *     it is read; the results are bit-identical over zero, 0xFF and 0x7F
+ *     bytes), and the same holds for the whole workspace of every other
+ *     scoring / top-K entry point, the exclusion-list builder and the sampler;
+ *   - every call, on every path and plan and of every form that shares this
+ *     layout (_pool, _pool2, _excl, CARS2, AFM without attention), leaves the
+ *     prefix zero: only the small-catalog kernel writes there, and it re-arms
+ *     its counters; no region of any plan lies below HHFM_CATALOG_WS_ZERO;
+ *   - one workspace serves any sequence of calls it is large enough for,
+ *     whatever their B, item_count, K, dtype, mode and plan.
+ * A prefix that is NOT zero is a caller error the library cannot see: the
+ * partial lists are then merged by the wrong workgroup or by none (wrong or
+ * unwritten output, HHFM_OK returned).
  * ---------------------------------------------------------------------- */
 int hhfm_catalog_topk_workspace(int64_t B, int32_t item_count, int32_t k,
                                 int32_t K, size_t* ws_bytes);

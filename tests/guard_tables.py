@@ -11,6 +11,10 @@ keep it *harmless*:
   changes a pad, which ``pads_untouched`` finds by comparing bit patterns.
 * ``guarded_workspace(nbytes)`` does the same for a byte workspace: guards of
   0xA5 bytes around the ``nbytes`` the entry point is told about.
+* ``poisoned_workspace(nbytes, fill, zero_prefix)`` is the same buffer with its
+  interior filled with a poison byte instead of zeros (the workspace-contract
+  tests, tests/test_gpu_workspace_contract.py): a kernel that reads scratch it
+  never wrote then computes with the poison.
 * ``near_miss_ids(M, P)`` are the only bad ids the tests use: −P … −1 and
   M … M + P − 1.  With pads of at least ``P`` rows an unclamped access lands in
   memory this module allocated.
@@ -26,6 +30,18 @@ PAD_ROWS = 8            # P: rows of padding, and the reach of the near-miss ids
 PAD_ALIGN = 256         # pad bytes are a multiple of this: the view keeps the buffer's alignment
 WS_GUARD = 4096         # guard bytes on each side of a workspace
 WS_FILL = 0xA5
+# Poison bytes for scratch that "may hold anything" (include/hhfm.h).  Two, so
+# that a stale word is wrong whichever way the kernel compares it:
+# 0xFF bytes: a 64-bit entry key above every real one (0xffff...), an fp32 /
+#   bf16 NaN, int32 -1 (an id or offset below every range), and an arrival
+#   counter that never reaches S (0xffffffff + S wraps far below it).
+# 0x7F bytes: fp32 0x7f7f7f7f = +3.39e38, a finite score that beats every real
+#   one where NaN would drop out of a max — the mirror of the 0x80 fill the
+#   streaming path gives its threshold hints (-3.39e38) —, and a huge positive
+#   key / index.
+POISON_FF = 0xFF
+POISON_7F = 0x7F
+POISONS = (POISON_FF, POISON_7F)
 
 # quiet NaN, as an integer of the element's width
 _NAN_BITS = {torch.float32: (torch.int32, 0x7fc00000), torch.bfloat16: (torch.int16, 0x7fc0)}
@@ -73,6 +89,18 @@ def guarded_workspace(nbytes, device, guard=WS_GUARD):
     return view, buffer
 
 
+def poisoned_workspace(nbytes, device, fill, zero_prefix=0, guard=WS_GUARD):
+    """-> (view, buffer): ``guarded_workspace``'s layout (0xA5 guards on both
+    sides of exactly ``nbytes``), the interior filled with the byte ``fill``
+    except its first ``zero_prefix`` bytes, which are zero."""
+    assert guard % PAD_ALIGN == 0 and 0 <= zero_prefix and 0 <= fill <= 0xFF
+    buffer = torch.full((guard + nbytes + guard,), WS_FILL, dtype=torch.uint8, device=device)
+    view = buffer[guard:guard + nbytes]
+    view.fill_(fill)
+    view[:min(zero_prefix, nbytes)].zero_()
+    return view, buffer
+
+
 def pads_untouched(buffer, view):
     """True when every element of ``buffer`` outside ``view`` still holds the
     fill pattern (compared as integers: NaN != NaN as floats)."""
@@ -97,6 +125,11 @@ class Guards:
 
     def workspace(self, nbytes, device):
         view, buffer = guarded_workspace(nbytes, device)
+        self.pairs.append((view, buffer))
+        return view
+
+    def poisoned(self, nbytes, device, fill, zero_prefix=0):
+        view, buffer = poisoned_workspace(nbytes, device, fill, zero_prefix)
         self.pairs.append((view, buffer))
         return view
 

@@ -31,6 +31,18 @@ DESIGNS = [
     ("one_per_split", dict(N=65549, k=64, dtype="bf16", mode="hhfm", K=20)),
     ("periodic", dict(N=65549, k=64, dtype="f32", mode="hhfm", sentinels=(4100, 50001))),
     ("plateau_spikes", dict(N=4082, k=64, dtype="f32", mode="hhfm", ctx_on_items=True)),
+    # the sizes of tests/test_gpu_workspace_contract.py: the fused kernel's range
+    # counts (1,024 .. 16,384), the smallest streaming (16,385) and seeded (65,536) catalogs
+    ("plateau_spikes", dict(N=1024, k=16, dtype="f32", mode="fm", m=33)),
+    ("plateau_spikes", dict(N=1025, k=64, dtype="bf16", mode="hhfm", m=65)),
+    ("one_per_split", dict(N=1024, k=64, dtype="bf16", mode="fm", K=32)),
+    ("one_per_split", dict(N=4097, k=16, dtype="f32", mode="hhfm", K=64)),
+    ("ascending", dict(N=4096, k=64, dtype="bf16", mode="fm")),
+    ("ascending", dict(N=16384, k=16, dtype="f32", mode="hhfm")),
+    ("ascending", dict(N=16385, k=64, dtype="bf16", mode="hhfm")),
+    ("one_per_split", dict(N=16385, k=16, dtype="f32", mode="fm", K=64)),
+    ("ascending", dict(N=65536, k=16, dtype="f32", mode="fm")),
+    ("plateau_spikes", dict(N=65536, k=128, dtype="bf16", mode="hhfm", m=65)),
 ]
 IDS = [f"{d}-" + "-".join(f"{k}{v}" for k, v in kw.items()) for d, kw in DESIGNS]
 

@@ -16,6 +16,8 @@
 //     the xor-8/4/2/1 steps are v_add_f32_dpp (row_ror / quad_perm) and only
 //     the xor-32/16 steps of LPR 64 / 32 go through ds_bpermute_b32 (LDS
 //     hardware, no LDS allocation).  No atomics, one fp32 store per row.
+#include <type_traits>
+
 #include "hhfm_common.h"
 #include "hhfm_feature.h"
 
@@ -1018,228 +1020,203 @@ static int grid_for(int64_t rows, int64_t rows_per_block, hipStream_t s) {
   return (int)g;
 }
 
+// every row kernel's launch: `grid` blocks of 256 threads on `s`
+template <class Kernel, class... Args>
+static void launch_rows(Kernel kernel, int grid, hipStream_t s, Args... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, args...);
+}
+
+// rows a 256-thread block takes per iteration: 4 waves x 64 / LPR groups x U slots
+constexpr int rows_per_block(int lpr, int u) { return 4 * (kWave / lpr) * u; }
+
+// rows far beyond the caches (a table of 1 GiB or more): the user / item rows
+// are streamed (fm_rows_fast NTM 2, fm_rows_fast_hot NT01)
+static bool big_table(int64_t M, int lpr) { return M * (int64_t)lpr * 16 >= ((int64_t)1 << 30); }
+
+// The fast kernels' template arguments from the run-time shape: fn(F, LPR,
+// BF16) is called with std::integral_constants for F in FS..., lpr (16-byte
+// chunks per row) in {4, 8, 16, 32, 64} and the dtype, and its result
+// returned; false without a call: no kernel for the shape.
+template <int... FS>
+struct FSet {};
+using FastF = FSet<2, 3, 4, 5, 6, 7, 8, 10, 12>;
+using HotF = FSet<3, 4, 5, 6, 7, 8>;    // fm_rows_fast_hot
+// hybrid_rows_two_way, the reference's layouts: F = 5 with 3 context columns
+// (frappe), 10 with 5 + 3 time (jiaju), 12 with 5 + 5 (resturant)
+using TwoWayF = FSet<5, 10, 12>;
+constexpr int two_way_nctx(int F) { return F == 5 ? 3 : 5; }
+
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+template <int... FS, class Fn>
+static bool dispatch_rows(FSet<FS...>, int F, int lpr, bool bf16, Fn fn) {
+  auto on_lpr = [&](auto f, auto b) -> bool {
+    switch (lpr) {
+      case 4: return fn(f, int_c<4>{}, b);
+      case 8: return fn(f, int_c<8>{}, b);
+      case 16: return fn(f, int_c<16>{}, b);
+      case 32: return fn(f, int_c<32>{}, b);
+      case 64: return fn(f, int_c<64>{}, b);
+      default: return false;
+    }
+  };
+  auto on_f = [&](auto f) -> bool {
+    return bf16 ? on_lpr(f, std::true_type{}) : on_lpr(f, std::false_type{});
+  };
+  bool done = false;
+  (void)((F == FS && ((done = on_f(int_c<FS>{})), true)) || ...);
+  return done;
+}
+
 // fm_rows_fast_hot: launched when `forced` (HHFM_FLAG_HOT_TAIL) or when its
 // own grid is at the cap, so that every wave loops and the 16 KiB staging per
-// workgroup is amortised; returns false (nothing launched) otherwise.  A
-// forced launch below that size takes a quarter of the uncapped blocks, so
-// its waves iterate too.
-template <int F, int LPR, bool BF16>
-static bool launch_fm_hot(const int32_t* idx, int64_t B, const char* E,
-                          int64_t M, const float* w, float w0, float* out,
-                          bool forced, int32_t* status, hipStream_t s) {
-  constexpr int RPB = 4 * (kWave / LPR) * HotRows<F>::U;
-  const int64_t blocks = (B + RPB - 1) / RPB;
-  const int64_t cap = (int64_t)stream_cu_count(s) * HHFM_K1_HOT_CAP;
-  if (blocks < cap && !forced) return false;
-  int64_t g = blocks >= cap ? cap : blocks / 4;
-  if (g < 1) g = 1;
-  const int grid = (int)g;
-  const bool big = M * (int64_t)LPR * 16 >= ((int64_t)1 << 30);
-  if (w && big)
-    hipLaunchKernelGGL((fm_rows_fast_hot<F, LPR, BF16, true, true>), dim3(grid),
-                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status);
-  else if (w)
-    hipLaunchKernelGGL((fm_rows_fast_hot<F, LPR, BF16, true, false>), dim3(grid),
-                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status);
-  else
-    hipLaunchKernelGGL((fm_rows_fast_hot<F, LPR, BF16, false, false>), dim3(grid),
-                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status);
-  return true;
-}
-
-template <int F, int LPR, bool BF16>
-static void launch_fm_fast(const int32_t* idx, int64_t B, const char* E,
-                           int64_t M, const float* w, float w0, float* out,
-                           bool nt, int32_t* status, hipStream_t s) {
-  constexpr int RPB = 4 * (kWave / LPR) * RowsPerLane<F>::value;
-  const int grid = grid_for(B, RPB, s);
-  // rows far beyond the caches: the user / item rows streamed (NTM 2)
-  const bool big = M * (int64_t)LPR * 16 >= ((int64_t)1 << 30);
-  if (w && nt)
-    hipLaunchKernelGGL((fm_rows_fast<F, LPR, BF16, true, 1>), dim3(grid),
-                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status, nullptr);
-  else if (w && big && F >= 2)
-    hipLaunchKernelGGL((fm_rows_fast<F, LPR, BF16, true, 2>), dim3(grid),
-                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status, nullptr);
-  else if (w)
-    hipLaunchKernelGGL((fm_rows_fast<F, LPR, BF16, true, 0>), dim3(grid),
-                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status, nullptr);
-  else
-    hipLaunchKernelGGL((fm_rows_fast<F, LPR, BF16, false, 0>), dim3(grid),
-                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status, nullptr);
-}
-
-// fm_rows_fast<SCALED>: the plain launcher's grid and its rule for tables of
-// 1 GiB and more (NTM 2); no flags, never the LDS-tail kernel
-template <int F, int LPR, bool BF16>
-static void launch_fm_scaled(const int32_t* idx, int64_t B, const char* E,
-                             int64_t M, const float* w, float w0, const float* scale,
-                             float* out, int32_t* status, hipStream_t s) {
-  constexpr int RPB = 4 * (kWave / LPR) * RowsPerLane<F>::value;
-  const int grid = grid_for(B, RPB, s);
-  const bool big = M * (int64_t)LPR * 16 >= ((int64_t)1 << 30);
-  if (w && big && F >= 2)
-    hipLaunchKernelGGL((fm_rows_fast<F, LPR, BF16, true, 2, true>), dim3(grid),
-                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status, scale);
-  else if (w)
-    hipLaunchKernelGGL((fm_rows_fast<F, LPR, BF16, true, 0, true>), dim3(grid),
-                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status, scale);
-  else
-    hipLaunchKernelGGL((fm_rows_fast<F, LPR, BF16, false, 0, true>), dim3(grid),
-                       dim3(256), 0, s, idx, B, E, M, w, w0, out, status, scale);
-}
-
-template <int F, int LPR, bool BF16>
-static void launch_hybrid_fast(const int32_t* idx, int64_t B, int nctx,
-                               const char* E, int64_t M, float* out,
-                               int32_t* status, hipStream_t s) {
-  constexpr int RPB = 4 * (kWave / LPR) * RowsPerLane<F>::value;
-  const int grid = grid_for(B, RPB, s);
-  hipLaunchKernelGGL((hybrid_rows_fast<F, LPR, BF16>), dim3(grid), dim3(256), 0,
-                     s, idx, B, nctx, E, M, out, status);
-}
-
-template <int F, int LPR, bool BF16>
-static void launch_hybrid_pool(const int32_t* idx, int64_t B, int nctx,
-                               const char* E, int64_t M, float* out, PoolModes pm,
-                               int32_t* status, hipStream_t s) {
-  constexpr int RPB = 4 * (kWave / LPR) * RowsPerLane<F>::value;
-  const int grid = grid_for(B, RPB, s);
-  hipLaunchKernelGGL((hybrid_rows_pool<F, LPR, BF16>), dim3(grid), dim3(256), 0,
-                     s, idx, B, nctx, E, M, out, pm, status);
-}
-
-// dispatch on LPR (16-byte chunks per row) for a fixed F and dtype
-#define HHFM_LPR_SWITCH(LAUNCH, F, BF16, ...)            \
-  switch (lpr) {                                         \
-    case 4: LAUNCH<F, 4, BF16>(__VA_ARGS__); break;      \
-    case 8: LAUNCH<F, 8, BF16>(__VA_ARGS__); break;      \
-    case 16: LAUNCH<F, 16, BF16>(__VA_ARGS__); break;    \
-    case 32: LAUNCH<F, 32, BF16>(__VA_ARGS__); break;    \
-    case 64: LAUNCH<F, 64, BF16>(__VA_ARGS__); break;    \
-    default: return false;                               \
-  }
-
-#define HHFM_F_SWITCH(LAUNCH, BF16, ...)                          \
-  switch (F) {                                                    \
-    case 2: HHFM_LPR_SWITCH(LAUNCH, 2, BF16, __VA_ARGS__) break;   \
-    case 3: HHFM_LPR_SWITCH(LAUNCH, 3, BF16, __VA_ARGS__) break;   \
-    case 4: HHFM_LPR_SWITCH(LAUNCH, 4, BF16, __VA_ARGS__) break;   \
-    case 5: HHFM_LPR_SWITCH(LAUNCH, 5, BF16, __VA_ARGS__) break;   \
-    case 6: HHFM_LPR_SWITCH(LAUNCH, 6, BF16, __VA_ARGS__) break;   \
-    case 7: HHFM_LPR_SWITCH(LAUNCH, 7, BF16, __VA_ARGS__) break;   \
-    case 8: HHFM_LPR_SWITCH(LAUNCH, 8, BF16, __VA_ARGS__) break;   \
-    case 10: HHFM_LPR_SWITCH(LAUNCH, 10, BF16, __VA_ARGS__) break; \
-    case 12: HHFM_LPR_SWITCH(LAUNCH, 12, BF16, __VA_ARGS__) break; \
-    default: return false;                                        \
-  }
-
-static bool try_fm_fast(const int32_t* idx, int64_t B, int F, const char* E,
-                        int64_t M, int lpr, bool bf16, const float* w, float w0,
-                        float* out, bool nt, int32_t* status, hipStream_t s) {
-  if (bf16) {
-    HHFM_F_SWITCH(launch_fm_fast, true, idx, B, E, M, w, w0, out, nt, status, s)
-  } else {
-    HHFM_F_SWITCH(launch_fm_fast, false, idx, B, E, M, w, w0, out, nt, status, s)
-  }
-  return true;
-}
-
-static bool try_fm_scaled(const int32_t* idx, int64_t B, int F, const char* E,
-                          int64_t M, int lpr, bool bf16, const float* w, float w0,
-                          const float* scale, float* out, int32_t* status, hipStream_t s) {
-  if (bf16) {
-    HHFM_F_SWITCH(launch_fm_scaled, true, idx, B, E, M, w, w0, scale, out, status, s)
-  } else {
-    HHFM_F_SWITCH(launch_fm_scaled, false, idx, B, E, M, w, w0, scale, out, status, s)
-  }
-  return true;
-}
-
-#define HHFM_F_SWITCH_HOT(BF16, ...)                                            \
-  switch (F) {                                                                 \
-    case 3: HHFM_LPR_SWITCH(return launch_fm_hot, 3, BF16, __VA_ARGS__) break; \
-    case 4: HHFM_LPR_SWITCH(return launch_fm_hot, 4, BF16, __VA_ARGS__) break; \
-    case 5: HHFM_LPR_SWITCH(return launch_fm_hot, 5, BF16, __VA_ARGS__) break; \
-    case 6: HHFM_LPR_SWITCH(return launch_fm_hot, 6, BF16, __VA_ARGS__) break; \
-    case 7: HHFM_LPR_SWITCH(return launch_fm_hot, 7, BF16, __VA_ARGS__) break; \
-    case 8: HHFM_LPR_SWITCH(return launch_fm_hot, 8, BF16, __VA_ARGS__) break; \
-    default: return false;                                                     \
-  }
-
-// true: fm_rows_fast_hot launched; false: no such kernel for this shape, or
-// (not forced) a call too small for it
+// workgroup is amortised; false (nothing launched) otherwise, or where no such
+// kernel exists for the shape.  A forced launch below that size takes a
+// quarter of the uncapped blocks, so its waves iterate too.
 static bool try_fm_hot(const int32_t* idx, int64_t B, int F, const char* E,
                        int64_t M, int lpr, bool bf16, const float* w, float w0,
                        float* out, bool forced, int32_t* status, hipStream_t s) {
-  if (bf16) {
-    HHFM_F_SWITCH_HOT(true, idx, B, E, M, w, w0, out, forced, status, s)
-  } else {
-    HHFM_F_SWITCH_HOT(false, idx, B, E, M, w, w0, out, forced, status, s)
-  }
-  return false;
+  return dispatch_rows(HotF{}, F, lpr, bf16, [&](auto f, auto l, auto b) {
+    constexpr int NF = decltype(f)::value, LPR = decltype(l)::value;
+    constexpr bool BF16 = decltype(b)::value;
+    constexpr int RPB = rows_per_block(LPR, HotRows<NF>::U);
+    const int64_t blocks = (B + RPB - 1) / RPB;
+    const int64_t cap = (int64_t)stream_cu_count(s) * HHFM_K1_HOT_CAP;
+    if (blocks < cap && !forced) return false;
+    int64_t g = blocks >= cap ? cap : blocks / 4;
+    if (g < 1) g = 1;
+    auto kernel = !w                 ? fm_rows_fast_hot<NF, LPR, BF16, false, false>
+                  : big_table(M, LPR) ? fm_rows_fast_hot<NF, LPR, BF16, true, true>
+                                      : fm_rows_fast_hot<NF, LPR, BF16, true, false>;
+    launch_rows(kernel, (int)g, s, idx, B, E, M, w, w0, out, status);
+    return true;
+  });
 }
 
+// fm_rows_fast, SCALED where `scale` is given.  nt: HHFM_FLAG_STREAM_TABLE
+// (NTM 1; the scaled entry point has no flags, so no such kernel); else a big
+// table streams its user / item rows (NTM 2).  Without `w` neither applies.
+static bool try_fm_fast(const int32_t* idx, int64_t B, int F, const char* E,
+                        int64_t M, int lpr, bool bf16, const float* w, float w0,
+                        const float* scale, float* out, bool nt, int32_t* status,
+                        hipStream_t s) {
+  return dispatch_rows(FastF{}, F, lpr, bf16, [&](auto f, auto l, auto b) {
+    constexpr int NF = decltype(f)::value, LPR = decltype(l)::value;
+    constexpr bool BF16 = decltype(b)::value;
+    const int grid = grid_for(B, rows_per_block(LPR, RowsPerLane<NF>::value), s);
+    const bool big = big_table(M, LPR);
+    auto launch = [&](auto scaled) {
+      constexpr bool SC = decltype(scaled)::value;
+      auto kernel = !w    ? fm_rows_fast<NF, LPR, BF16, false, 0, SC>
+                    : big ? fm_rows_fast<NF, LPR, BF16, true, 2, SC>
+                          : fm_rows_fast<NF, LPR, BF16, true, 0, SC>;
+      if constexpr (!SC) {
+        if (w && nt) kernel = fm_rows_fast<NF, LPR, BF16, true, 1>;
+      }
+      launch_rows(kernel, grid, s, idx, B, E, M, w, w0, out, status, scale);
+    };
+    if (scale) launch(std::true_type{});
+    else launch(std::false_type{});
+    return true;
+  });
+}
+
+// hybrid_rows_fast, or hybrid_rows_pool where `pm` is given
 static bool try_hybrid_fast(const int32_t* idx, int64_t B, int F, int nctx,
                             const char* E, int64_t M, int lpr, bool bf16,
-                            float* out, int32_t* status, hipStream_t s) {
-  if (bf16) {
-    HHFM_F_SWITCH(launch_hybrid_fast, true, idx, B, nctx, E, M, out, status, s)
-  } else {
-    HHFM_F_SWITCH(launch_hybrid_fast, false, idx, B, nctx, E, M, out, status, s)
-  }
-  return true;
+                            float* out, const PoolModes* pm, int32_t* status,
+                            hipStream_t s) {
+  return dispatch_rows(FastF{}, F, lpr, bf16, [&](auto f, auto l, auto b) {
+    constexpr int NF = decltype(f)::value, LPR = decltype(l)::value;
+    constexpr bool BF16 = decltype(b)::value;
+    const int grid = grid_for(B, rows_per_block(LPR, RowsPerLane<NF>::value), s);
+    if (pm)
+      launch_rows(hybrid_rows_pool<NF, LPR, BF16>, grid, s, idx, B, nctx, E, M, out, *pm, status);
+    else
+      launch_rows(hybrid_rows_fast<NF, LPR, BF16>, grid, s, idx, B, nctx, E, M, out, status);
+    return true;
+  });
 }
 
-static bool try_hybrid_pool(const int32_t* idx, int64_t B, int F, int nctx,
-                            const char* E, int64_t M, int lpr, bool bf16,
-                            float* out, PoolModes pm, int32_t* status, hipStream_t s) {
-  if (bf16) {
-    HHFM_F_SWITCH(launch_hybrid_pool, true, idx, B, nctx, E, M, out, pm, status, s)
-  } else {
-    HHFM_F_SWITCH(launch_hybrid_pool, false, idx, B, nctx, E, M, out, pm, status, s)
-  }
-  return true;
-}
-
-template <int F, int NCTX, int LPR, bool BF16>
-static void launch_two_way(const int32_t* idx, int64_t B, const char* E, int64_t M, float* out,
-                           PoolModes2 pm, int32_t* status, hipStream_t s) {
-  constexpr int RPB = 4 * (kWave / LPR) * RowsPerLane<F>::value;
-  const int grid = grid_for(B, RPB, s);
-  hipLaunchKernelGGL((hybrid_rows_two_way<F, NCTX, LPR, BF16>), dim3(grid), dim3(256), 0, s,
-                     idx, B, E, M, out, pm, status);
-}
-
-template <int F, int NCTX, bool BF16>
-static bool two_way_lpr(int lpr, const int32_t* idx, int64_t B, const char* E, int64_t M,
-                        float* out, PoolModes2 pm, int32_t* status, hipStream_t s) {
-  switch (lpr) {
-    case 4: launch_two_way<F, NCTX, 4, BF16>(idx, B, E, M, out, pm, status, s); return true;
-    case 8: launch_two_way<F, NCTX, 8, BF16>(idx, B, E, M, out, pm, status, s); return true;
-    case 16: launch_two_way<F, NCTX, 16, BF16>(idx, B, E, M, out, pm, status, s); return true;
-    case 32: launch_two_way<F, NCTX, 32, BF16>(idx, B, E, M, out, pm, status, s); return true;
-    case 64: launch_two_way<F, NCTX, 64, BF16>(idx, B, E, M, out, pm, status, s); return true;
-    default: return false;
-  }
-}
-
-// the fast two-way kernel exists for the reference's layouts: 3 context
-// columns (frappe), 5 + 3 time (jiaju), 5 + 5 (resturant); false: no such kernel
-template <bool BF16>
 static bool try_two_way(const int32_t* idx, int64_t B, int F, int nctx, const char* E,
-                        int64_t M, int lpr, float* out, PoolModes2 pm, int32_t* status,
-                        hipStream_t s) {
-  if (F == 5 && nctx == 3) return two_way_lpr<5, 3, BF16>(lpr, idx, B, E, M, out, pm, status, s);
-  if (F == 10 && nctx == 5) return two_way_lpr<10, 5, BF16>(lpr, idx, B, E, M, out, pm, status, s);
-  if (F == 12 && nctx == 5) return two_way_lpr<12, 5, BF16>(lpr, idx, B, E, M, out, pm, status, s);
-  return false;
+                        int64_t M, int lpr, bool bf16, float* out, PoolModes2 pm,
+                        int32_t* status, hipStream_t s) {
+  return dispatch_rows(TwoWayF{}, F, lpr, bf16, [&](auto f, auto l, auto b) {
+    constexpr int NF = decltype(f)::value, LPR = decltype(l)::value;
+    constexpr bool BF16 = decltype(b)::value;
+    if (nctx != two_way_nctx(NF)) return false;
+    launch_rows(hybrid_rows_two_way<NF, two_way_nctx(NF), LPR, BF16>,
+                grid_for(B, rows_per_block(LPR, RowsPerLane<NF>::value), s), s, idx, B, E, M, out,
+                pm, status);
+    return true;
+  });
 }
 
-static int lpr_for(int64_t k, int dtype) {
+// 16-byte chunks per row; 0: no fast kernel reads this table (rows that are
+// no whole chunks, or E not 16-byte aligned)
+static int lpr_for(const void* E, int64_t k, int dtype) {
   const int64_t row_bytes = k * (dtype == HHFM_BF16 ? 2 : 4);
-  if (row_bytes % 16) return 0;
+  if (row_bytes % 16 || (reinterpret_cast<uintptr_t>(E) & 15)) return 0;
   return (int)(row_bytes / 16);
+}
+
+// The argument checks of hhfm_fm_score_rows_ex and _scaled in their order:
+// shape, dtype, the entry point's own check (`own_ok`: its flags, its scale),
+// then — past the empty batch — the pointers.  The caller returns on any code
+// but HHFM_OK, and on B == 0.
+static int check_fm_args(const int32_t* idx, int64_t B, int F, const void* E, int64_t M, int k,
+                         int dtype, const float* out, bool own_ok) {
+  if (B < 0 || F < 1 || F > 64 || k < 1 || M < 1) return HHFM_EINVAL;
+  if (dtype != HHFM_F32 && dtype != HHFM_BF16) return HHFM_EINVAL;
+  if (!own_ok) return HHFM_EINVAL;
+  if (B > 0 && (!idx || !E || !out)) return HHFM_EINVAL;
+  return HHFM_OK;
+}
+
+// fm_rows_fast where it exists for the shape, fm_rows_generic otherwise
+static int launch_fm_rows(const int32_t* idx, int64_t B, int F, const char* E, int64_t M, int k,
+                          int lpr, bool bf16, const float* w, float w0, const float* scale,
+                          float* out, bool nt, int32_t* status, hipStream_t s) {
+  if (!(lpr && try_fm_fast(idx, B, F, E, M, lpr, bf16, w, w0, scale, out, nt, status, s))) {
+    auto kernel = scale ? (bf16 ? fm_rows_generic<true, true> : fm_rows_generic<false, true>)
+                        : (bf16 ? fm_rows_generic<true> : fm_rows_generic<false>);
+    launch_rows(kernel, grid_for(B, 4, s), s, idx, B, F, E, M, k, w, w0, out, status, scale);
+  }
+  return (int)hipGetLastError();
+}
+
+// What hhfm_hybrid_score_rows_ex, _pool and _pool2 check, in their order:
+// shape, dtype, the columns and ranges, for _pool2 (`two_way`) the two-way
+// layout, then — past the empty batch — the pointers.  The caller returns on
+// any code but HHFM_OK, and on B == 0; otherwise `sh` is the launch's shape.
+struct HybridShape {
+  int nctx, ntime;
+  bool canonical;   // [user, item, ctx..., time...] spanning every column
+  int lpr;          // lpr_for
+  bool bf16;
+};
+
+static int check_hybrid_args(const int32_t* idx, int64_t B, int ncols, int user_col, int item_col,
+                             int ctx_begin, int ctx_end, int time_begin, int time_end,
+                             const void* E, int64_t M, int k, int dtype, const float* out,
+                             bool two_way, HybridShape& sh) {
+  if (B < 0 || ncols < 2 || ncols > 64 || k < 1 || M < 1) return HHFM_EINVAL;
+  if (dtype != HHFM_F32 && dtype != HHFM_BF16) return HHFM_EINVAL;
+  auto in_range = [&](int c) { return c >= 0 && c < ncols; };
+  if (!in_range(user_col) || !in_range(item_col)) return HHFM_EINVAL;
+  if (ctx_begin > ctx_end || time_begin > time_end) return HHFM_EINVAL;
+  if (ctx_end > ctx_begin && (!in_range(ctx_begin) || ctx_end > ncols)) return HHFM_EINVAL;
+  if (time_end > time_begin && (!in_range(time_begin) || time_end > ncols)) return HHFM_EINVAL;
+  sh.nctx = ctx_end - ctx_begin;
+  sh.ntime = time_end - time_begin;
+  if (two_way && !two_way_shape_ok(sh.nctx, sh.ntime)) return HHFM_EINVAL;
+  if (B > 0 && (!idx || !E || !out)) return HHFM_EINVAL;
+  sh.canonical = user_col == 0 && item_col == 1 && (sh.nctx == 0 || ctx_begin == 2) &&
+                 (sh.ntime == 0 || time_begin == 2 + sh.nctx) && 2 + sh.nctx + sh.ntime == ncols;
+  sh.lpr = lpr_for(E, k, dtype);
+  sh.bf16 = dtype == HHFM_BF16;
+  return HHFM_OK;
 }
 
 // the generic fall-back of the three hhfm_hybrid_score_rows* entry points
@@ -1249,8 +1226,8 @@ static void launch_hybrid_generic(Feature feat, const int32_t* idx, int64_t B, i
                                   int64_t M, int k, bool bf16, float* out, int32_t* status,
                                   hipStream_t s) {
   auto kernel = bf16 ? hybrid_rows_generic<true, Feature> : hybrid_rows_generic<false, Feature>;
-  hipLaunchKernelGGL(kernel, dim3(grid_for(B, 4, s)), dim3(256), 0, s, idx, B, ncols, ucol, icol,
-                     c0, c1, t0, t1, E, M, k, out, feat, status);
+  launch_rows(kernel, grid_for(B, 4, s), s, idx, B, ncols, ucol, icol, c0, c1, t0, t1, E, M, k,
+              out, feat, status);
 }
 
 }  // namespace hhfm
@@ -1262,42 +1239,26 @@ extern "C" int hhfm_fm_score_rows_ex(const int32_t* idx, int64_t B, int32_t F,
                                      int32_t dtype, const float* w, float w0,
                                      float* out, int32_t flags, int32_t* status,
                                      void* stream) {
-  if (B < 0 || F < 1 || F > 64 || k < 1 || features_M < 1) return HHFM_EINVAL;
-  if (dtype != HHFM_F32 && dtype != HHFM_BF16) return HHFM_EINVAL;
-  if (flags & ~(HHFM_FLAG_STREAM_TABLE | HHFM_FLAG_HOT_TAIL | HHFM_FLAG_NO_HOT_TAIL))
-    return HHFM_EINVAL;
   const bool hot_forced = (flags & HHFM_FLAG_HOT_TAIL) != 0;
+  const bool hot_refused = (flags & (HHFM_FLAG_NO_HOT_TAIL | HHFM_FLAG_STREAM_TABLE)) != 0;
   // the LDS-tail kernel has no all-streaming plan, and cannot be both forced and refused
-  if (hot_forced && (flags & (HHFM_FLAG_NO_HOT_TAIL | HHFM_FLAG_STREAM_TABLE))) return HHFM_EINVAL;
-  if (B == 0) return HHFM_OK;
-  if (!idx || !E || !out) return HHFM_EINVAL;
+  const bool flags_ok =
+      !(flags & ~(HHFM_FLAG_STREAM_TABLE | HHFM_FLAG_HOT_TAIL | HHFM_FLAG_NO_HOT_TAIL)) &&
+      !(hot_forced && hot_refused);
+  const int rc = check_fm_args(idx, B, F, E, features_M, k, dtype, out, flags_ok);
+  if (rc != HHFM_OK || B == 0) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const char* Eb = reinterpret_cast<const char*>(E);
   const bool bf16 = dtype == HHFM_BF16;
-  const int lpr = lpr_for(k, dtype);
-  const bool aligned = (reinterpret_cast<uintptr_t>(E) & 15) == 0;
+  const int lpr = lpr_for(E, k, dtype);
   if (HHFM_K1_HOT_AUTO || hot_forced) {
-    const bool allowed = !(flags & (HHFM_FLAG_NO_HOT_TAIL | HHFM_FLAG_STREAM_TABLE));
-    if (allowed && lpr && aligned &&
-        try_fm_hot(idx, B, F, reinterpret_cast<const char*>(E), features_M, lpr, bf16, w, w0,
-                   out, hot_forced, status, s))
+    if (!hot_refused && lpr &&
+        try_fm_hot(idx, B, F, Eb, features_M, lpr, bf16, w, w0, out, hot_forced, status, s))
       return (int)hipGetLastError();
     if (hot_forced) return HHFM_EUNSUPPORTED;   // F outside 3..8, or rows not whole 16-B chunks
   }
-  if (!(lpr && aligned &&
-        try_fm_fast(idx, B, F, reinterpret_cast<const char*>(E), features_M,
-                    lpr, bf16, w, w0, out, (flags & HHFM_FLAG_STREAM_TABLE) != 0, status,
-                    s))) {
-    const int grid = grid_for(B, 4, s);
-    if (bf16)
-      hipLaunchKernelGGL(fm_rows_generic<true>, dim3(grid), dim3(256), 0, s, idx,
-                         B, F, reinterpret_cast<const char*>(E), features_M, k,
-                         w, w0, out, status, nullptr);
-    else
-      hipLaunchKernelGGL(fm_rows_generic<false>, dim3(grid), dim3(256), 0, s,
-                         idx, B, F, reinterpret_cast<const char*>(E),
-                         features_M, k, w, w0, out, status, nullptr);
-  }
-  return (int)hipGetLastError();
+  return launch_fm_rows(idx, B, F, Eb, features_M, k, lpr, bf16, w, w0, nullptr, out,
+                        (flags & HHFM_FLAG_STREAM_TABLE) != 0, status, s);
 }
 
 extern "C" int hhfm_fm_score_rows_scaled(const int32_t* idx, int64_t B, int32_t F,
@@ -1305,29 +1266,11 @@ extern "C" int hhfm_fm_score_rows_scaled(const int32_t* idx, int64_t B, int32_t 
                                          int32_t dtype, const float* w, float w0,
                                          const float* scale, float* out, int32_t* status,
                                          void* stream) {
-  if (B < 0 || F < 1 || F > 64 || k < 1 || features_M < 1) return HHFM_EINVAL;
-  if (dtype != HHFM_F32 && dtype != HHFM_BF16) return HHFM_EINVAL;
-  if (!scale) return HHFM_EINVAL;
-  if (B == 0) return HHFM_OK;
-  if (!idx || !E || !out) return HHFM_EINVAL;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const bool bf16 = dtype == HHFM_BF16;
-  const int lpr = lpr_for(k, dtype);
-  const bool aligned = (reinterpret_cast<uintptr_t>(E) & 15) == 0;
-  if (!(lpr && aligned &&
-        try_fm_scaled(idx, B, F, reinterpret_cast<const char*>(E), features_M, lpr, bf16, w,
-                      w0, scale, out, status, s))) {
-    const int grid = grid_for(B, 4, s);
-    if (bf16)
-      hipLaunchKernelGGL((fm_rows_generic<true, true>), dim3(grid), dim3(256), 0, s, idx, B, F,
-                         reinterpret_cast<const char*>(E), features_M, k, w, w0, out, status,
-                         scale);
-    else
-      hipLaunchKernelGGL((fm_rows_generic<false, true>), dim3(grid), dim3(256), 0, s, idx, B, F,
-                         reinterpret_cast<const char*>(E), features_M, k, w, w0, out, status,
-                         scale);
-  }
-  return (int)hipGetLastError();
+  const int rc = check_fm_args(idx, B, F, E, features_M, k, dtype, out, scale != nullptr);
+  if (rc != HHFM_OK || B == 0) return rc;
+  return launch_fm_rows(idx, B, F, reinterpret_cast<const char*>(E), features_M, k,
+                        lpr_for(E, k, dtype), dtype == HHFM_BF16, w, w0, scale, out, false, status,
+                        reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int hhfm_fm_score_rows(const int32_t* idx, int64_t B, int32_t F,
@@ -1346,36 +1289,17 @@ extern "C" int hhfm_hybrid_score_rows_ex(const int32_t* idx, int64_t B,
                                          int64_t features_M, int32_t k,
                                          int32_t dtype, float* out, int32_t* status,
                                          void* stream) {
-  if (B < 0 || ncols < 2 || ncols > 64 || k < 1 || features_M < 1)
-    return HHFM_EINVAL;
-  if (dtype != HHFM_F32 && dtype != HHFM_BF16) return HHFM_EINVAL;
-  auto in_range = [&](int c) { return c >= 0 && c < ncols; };
-  if (!in_range(user_col) || !in_range(item_col)) return HHFM_EINVAL;
-  if (ctx_begin > ctx_end || time_begin > time_end) return HHFM_EINVAL;
-  if (ctx_end > ctx_begin && (!in_range(ctx_begin) || ctx_end > ncols))
-    return HHFM_EINVAL;
-  if (time_end > time_begin && (!in_range(time_begin) || time_end > ncols))
-    return HHFM_EINVAL;
-  if (B == 0) return HHFM_OK;
-  if (!idx || !E || !out) return HHFM_EINVAL;
+  HybridShape sh;
+  const int rc = check_hybrid_args(idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
+                                   time_begin, time_end, E, features_M, k, dtype, out, false, sh);
+  if (rc != HHFM_OK || B == 0) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const bool bf16 = dtype == HHFM_BF16;
-  const int lpr = lpr_for(k, dtype);
-  const bool aligned = (reinterpret_cast<uintptr_t>(E) & 15) == 0;
-  const int nctx = ctx_end - ctx_begin;
-  const int ntime = time_end - time_begin;
-  // canonical layout: [user, item, ctx..., time...] spanning every column
-  const bool canonical = user_col == 0 && item_col == 1 &&
-                         (nctx == 0 || ctx_begin == 2) &&
-                         (ntime == 0 || time_begin == 2 + nctx) &&
-                         2 + nctx + ntime == ncols;
-  if (!(canonical && lpr && aligned &&
-        try_hybrid_fast(idx, B, ncols, nctx,
-                        reinterpret_cast<const char*>(E), features_M, lpr,
-                        bf16, out, status, s)))
+  const char* Eb = reinterpret_cast<const char*>(E);
+  if (!(sh.canonical && sh.lpr &&
+        try_hybrid_fast(idx, B, ncols, sh.nctx, Eb, features_M, sh.lpr, sh.bf16, out, nullptr,
+                        status, s)))
     launch_hybrid_generic(SumFeature{}, idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
-                          time_begin, time_end, reinterpret_cast<const char*>(E), features_M, k,
-                          bf16, out, status, s);
+                          time_begin, time_end, Eb, features_M, k, sh.bf16, out, status, s);
   return (int)hipGetLastError();
 }
 
@@ -1408,34 +1332,17 @@ extern "C" int hhfm_hybrid_score_rows_pool(const int32_t* idx, int64_t B,
     return hhfm_hybrid_score_rows_ex(idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
                                      time_begin, time_end, E, features_M, k, dtype, out,
                                      status, stream);
-  if (B < 0 || ncols < 2 || ncols > 64 || k < 1 || features_M < 1)
-    return HHFM_EINVAL;
-  if (dtype != HHFM_F32 && dtype != HHFM_BF16) return HHFM_EINVAL;
-  auto in_range = [&](int c) { return c >= 0 && c < ncols; };
-  if (!in_range(user_col) || !in_range(item_col)) return HHFM_EINVAL;
-  if (ctx_begin > ctx_end || time_begin > time_end) return HHFM_EINVAL;
-  if (ctx_end > ctx_begin && (!in_range(ctx_begin) || ctx_end > ncols))
-    return HHFM_EINVAL;
-  if (time_end > time_begin && (!in_range(time_begin) || time_end > ncols))
-    return HHFM_EINVAL;
-  if (B == 0) return HHFM_OK;
-  if (!idx || !E || !out) return HHFM_EINVAL;
+  HybridShape sh;
+  const int rc = check_hybrid_args(idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
+                                   time_begin, time_end, E, features_M, k, dtype, out, false, sh);
+  if (rc != HHFM_OK || B == 0) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const bool bf16 = dtype == HHFM_BF16;
-  const int lpr = lpr_for(k, dtype);
-  const bool aligned = (reinterpret_cast<uintptr_t>(E) & 15) == 0;
-  const int nctx = ctx_end - ctx_begin;
-  const int ntime = time_end - time_begin;
-  const bool canonical = user_col == 0 && item_col == 1 &&
-                         (nctx == 0 || ctx_begin == 2) &&
-                         (ntime == 0 || time_begin == 2 + nctx) &&
-                         2 + nctx + ntime == ncols;
-  if (!(canonical && lpr && aligned &&
-        try_hybrid_pool(idx, B, ncols, nctx, reinterpret_cast<const char*>(E),
-                        features_M, lpr, bf16, out, pm, status, s)))
+  const char* Eb = reinterpret_cast<const char*>(E);
+  if (!(sh.canonical && sh.lpr &&
+        try_hybrid_fast(idx, B, ncols, sh.nctx, Eb, features_M, sh.lpr, sh.bf16, out, &pm, status,
+                        s)))
     launch_hybrid_generic(PoolFeature{pm}, idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
-                          time_begin, time_end, reinterpret_cast<const char*>(E), features_M, k,
-                          bf16, out, status, s);
+                          time_begin, time_end, Eb, features_M, k, sh.bf16, out, status, s);
   return (int)hipGetLastError();
 }
 
@@ -1453,37 +1360,16 @@ extern "C" int hhfm_hybrid_score_rows_pool2(const int32_t* idx, int64_t B,
                                             void* stream) {
   PoolModes2 pm;
   if (!pooling2_unpack(pooling, pooling2, pm)) return HHFM_EINVAL;
-  if (B < 0 || ncols < 2 || ncols > 64 || k < 1 || features_M < 1)
-    return HHFM_EINVAL;
-  if (dtype != HHFM_F32 && dtype != HHFM_BF16) return HHFM_EINVAL;
-  auto in_range = [&](int c) { return c >= 0 && c < ncols; };
-  if (!in_range(user_col) || !in_range(item_col)) return HHFM_EINVAL;
-  if (ctx_begin > ctx_end || time_begin > time_end) return HHFM_EINVAL;
-  if (ctx_end > ctx_begin && (!in_range(ctx_begin) || ctx_end > ncols))
-    return HHFM_EINVAL;
-  if (time_end > time_begin && (!in_range(time_begin) || time_end > ncols))
-    return HHFM_EINVAL;
-  const int nctx = ctx_end - ctx_begin;
-  const int ntime = time_end - time_begin;
-  if (!two_way_shape_ok(nctx, ntime)) return HHFM_EINVAL;
-  if (B == 0) return HHFM_OK;
-  if (!idx || !E || !out) return HHFM_EINVAL;
+  HybridShape sh;
+  const int rc = check_hybrid_args(idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
+                                   time_begin, time_end, E, features_M, k, dtype, out, true, sh);
+  if (rc != HHFM_OK || B == 0) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const bool bf16 = dtype == HHFM_BF16;
-  const int lpr = lpr_for(k, dtype);
-  const bool aligned = (reinterpret_cast<uintptr_t>(E) & 15) == 0;
-  const bool canonical = user_col == 0 && item_col == 1 &&
-                         (nctx == 0 || ctx_begin == 2) &&
-                         (ntime == 0 || time_begin == 2 + nctx) &&
-                         2 + nctx + ntime == ncols;
   const char* Eb = reinterpret_cast<const char*>(E);
-  bool fast = false;
-  if (canonical && lpr && aligned)
-    fast = bf16 ? try_two_way<true>(idx, B, ncols, nctx, Eb, features_M, lpr, out, pm, status, s)
-                : try_two_way<false>(idx, B, ncols, nctx, Eb, features_M, lpr, out, pm, status, s);
-  if (!fast)
+  if (!(sh.canonical && sh.lpr &&
+        try_two_way(idx, B, ncols, sh.nctx, Eb, features_M, sh.lpr, sh.bf16, out, pm, status, s)))
     launch_hybrid_generic(TwoWayFeature{pm}, idx, B, ncols, user_col, item_col, ctx_begin, ctx_end,
-                          time_begin, time_end, Eb, features_M, k, bf16, out, status, s);
+                          time_begin, time_end, Eb, features_M, k, sh.bf16, out, status, s);
   return (int)hipGetLastError();
 }
 

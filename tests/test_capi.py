@@ -453,3 +453,127 @@ def test_train_workspace_sizes():
                              + r64((M + 3) // 4))
         sizes = [_afm_ws(lib, b, F, k, A, M) for b in (0, 1, 9, 1000)]
         assert sizes == sorted(sizes) and sizes[0] > state
+
+
+# ---------------------------------------------------------------------------
+# Row-scoring entry points: argument checks.  Every call below returns before
+# anything is launched (a check fails, or the batch is empty), so none of it
+# needs a device; the pointers are null or the never-dereferenced _D.
+# ---------------------------------------------------------------------------
+OK = 0
+_HYB_HEAD = [("idx", _vp), ("B", _i64), ("ncols", _i32), ("ucol", _i32), ("icol", _i32),
+             ("c0", _i32), ("c1", _i32), ("t0", _i32), ("t1", _i32), ("E", _vp), ("M", _i64),
+             ("k", _i32), ("dtype", _i32), ("out", _vp)]
+_HYB_TAIL = [("status", _vp), ("stream", _vp)]
+# entry point -> (symbol, its pooling-word arguments)
+_HYB = {"ex": ("hhfm_hybrid_score_rows_ex", ()),
+        "pool": ("hhfm_hybrid_score_rows_pool", ("pooling",)),
+        "pool2": ("hhfm_hybrid_score_rows_pool2", ("pooling", "pooling2"))}
+_POOL_MAX3 = 0x111          # max pooling for ctx, time and the final stack
+# Frappe layout [user, item, ctx x 3], an empty batch: valid for all three
+_HYB_BASE = dict(idx=None, B=0, ncols=5, ucol=0, icol=1, c0=2, c1=5, t0=0, t1=0, E=None, M=100,
+                 k=64, dtype=0, out=None, pooling=_POOL_MAX3, pooling2=_POOL_MAX3, status=None,
+                 stream=None)
+# (changed arguments, expected code) for every entry point
+_HYB_CASES = [
+    (dict(), OK),                                              # B == 0, null pointers
+    (dict(B=-1), EINVAL),
+    (dict(ncols=1), EINVAL),
+    (dict(ncols=65), EINVAL),
+    (dict(ncols=64), OK),
+    (dict(k=0), EINVAL),
+    (dict(M=0), EINVAL),
+    (dict(dtype=7), EINVAL),
+    (dict(dtype=1), OK),
+    (dict(ucol=5), EINVAL),
+    (dict(ucol=-1), EINVAL),
+    (dict(icol=5), EINVAL),
+    (dict(icol=-1), EINVAL),
+    (dict(c0=4, c1=2), EINVAL),                                # ctx_begin > ctx_end
+    (dict(t0=3, t1=1), EINVAL),
+    (dict(c1=6), EINVAL),                                      # ctx range past ncols
+    (dict(c0=-1), EINVAL),
+    (dict(c0=2, c1=3, t0=3, t1=6), EINVAL),                    # time range past ncols
+    (dict(c0=2, c1=3, t0=5, t1=7), EINVAL),
+    (dict(c0=7, c1=5, t0=9, t1=9), EINVAL),                    # ... whatever else is wrong
+    (dict(B=7), EINVAL),                                      # null pointers with B > 0
+    (dict(B=7, E=_D, out=_D), EINVAL),
+    (dict(B=7, idx=_D, out=_D), EINVAL),
+    (dict(B=7, idx=_D, E=_D), EINVAL),
+]
+# (entry point, changed arguments, expected code)
+_HYB_OWN_CASES = [
+    ("pool", dict(pooling=0), OK),                             # forwards to _ex
+    ("pool", dict(pooling=0, B=7), EINVAL),
+    ("pool", dict(pooling=0, ncols=65), EINVAL),
+    ("pool", dict(pooling=0x222), OK),
+    ("pool", dict(pooling=3), EINVAL),                         # no mode 3, even at B == 0
+    ("pool", dict(pooling=0x300), EINVAL),
+    ("pool", dict(pooling=0x1000), EINVAL),                    # a bit outside the word
+    ("pool", dict(pooling=-1), EINVAL),
+    ("pool2", dict(pooling=0, pooling2=0), OK),                # still the two-way model
+    ("pool2", dict(pooling=3), EINVAL),
+    ("pool2", dict(pooling=0x1000), EINVAL),
+    ("pool2", dict(pooling2=3), EINVAL),
+    ("pool2", dict(pooling2=0x030), EINVAL),
+    ("pool2", dict(pooling2=0x1000), EINVAL),
+    # one context column is no two-way layout: refused before the empty batch returns OK
+    ("ex", dict(ncols=3, c1=3), OK),
+    ("pool", dict(ncols=3, c1=3), OK),
+    ("pool2", dict(ncols=3, c1=3), EINVAL),
+    ("pool2", dict(ncols=6, c1=5, t0=5, t1=6), EINVAL),        # one time column
+    ("pool2", dict(ncols=2, c0=0, c1=0), EINVAL),              # no pool at all
+    ("ex", dict(c0=7, c1=7, t0=9, t1=9), OK),                  # empty ranges lie anywhere
+    ("pool", dict(c0=7, c1=7, t0=9, t1=9), OK),
+    ("pool2", dict(c0=7, c1=7, t0=9, t1=9), EINVAL),
+    ("pool2", dict(ncols=7, c1=5, t0=5, t1=7), OK),
+]
+
+
+def _hybrid_call(lib, which, **over):
+    sym, words = _HYB[which]
+    sig = _HYB_HEAD + [(w, _i32) for w in words] + _HYB_TAIL
+    f = getattr(lib, sym)
+    f.argtypes = [t for _, t in sig]
+    a = dict(_HYB_BASE, **over)
+    return f(*[a[n] for n, _ in sig])
+
+
+def test_hybrid_row_argument_errors_without_device():
+    """hhfm_hybrid_score_rows_ex / _pool / _pool2 check their arguments in the
+    same order with the same codes; the expected codes are those of the build
+    before the three shared one check."""
+    lib = ctypes.CDLL(LIB)
+    for which in _HYB:
+        for over, want in _HYB_CASES:
+            assert _hybrid_call(lib, which, **over) == want, (which, over)
+    for which, over, want in _HYB_OWN_CASES:
+        assert _hybrid_call(lib, which, **over) == want, (which, over)
+
+
+def test_fm_row_argument_errors_without_device():
+    """hhfm_fm_score_rows_scaled needs `scale` whatever B is; the flag rules
+    of hhfm_fm_score_rows_ex; a forced LDS-tail kernel that does not exist for
+    the shape is HHFM_EUNSUPPORTED, with nothing launched."""
+    lib = ctypes.CDLL(LIB)
+    sc = lib.hhfm_fm_score_rows_scaled
+    sc.argtypes = [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _f32, _vp, _vp, _vp, _vp]
+    assert sc(None, 0, 5, None, 10, 64, 0, None, 0.0, _D, None, None, None) == OK
+    assert sc(None, 0, 5, None, 10, 64, 0, None, 0.0, None, None, None, None) == EINVAL
+    assert sc(_D, 7, 5, _D, 10, 64, 0, None, 0.0, None, _D, None, None) == EINVAL
+    assert sc(None, 7, 5, None, 10, 64, 0, None, 0.0, _D, None, None, None) == EINVAL
+    assert sc(None, -1, 5, None, 10, 64, 0, None, 0.0, _D, None, None, None) == EINVAL
+    assert sc(None, 0, 65, None, 10, 64, 0, None, 0.0, _D, None, None, None) == EINVAL
+    assert sc(None, 0, 5, None, 10, 64, 7, None, 0.0, _D, None, None, None) == EINVAL
+    ex = lib.hhfm_fm_score_rows_ex
+    ex.argtypes = [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _f32, _vp, _i32, _vp, _vp]
+    STREAM, HOT, NO_HOT = 1, 2, 4
+    for flags in (0, STREAM, HOT, NO_HOT, STREAM | NO_HOT):
+        assert ex(None, 0, 5, None, 10, 64, 0, None, 0.0, None, flags, None, None) == OK
+        assert ex(None, 7, 5, None, 10, 64, 0, None, 0.0, None, flags, None, None) == EINVAL
+    for flags in (HOT | NO_HOT, HOT | STREAM, 8):              # even at B == 0
+        assert ex(None, 0, 5, None, 10, 64, 0, None, 0.0, None, flags, None, None) == EINVAL
+    # forced, and no LDS-tail kernel: F outside 3..8, rows that are no whole 16-byte chunks,
+    # a row width outside the kernel set, a table that is not 16-byte aligned
+    for F, k, E in ((2, 64, _D), (9, 64, _D), (5, 3, _D), (5, 20, _D), (5, 64, _D + 4)):
+        assert ex(_D, 7, F, E, 10, k, 0, None, 0.0, _D, HOT, None, None) == EUNSUPPORTED, (F, k)

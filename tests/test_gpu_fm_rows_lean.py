@@ -10,7 +10,7 @@ tests/test_gpu_kernels.py::test_fm_score_rows_parity (RTOL x Σ|terms|), and
 report BAD_ID exactly when a row holds a bad id — wherever in a wave's walk the
 hand-off to the general loop happens.
 
-Geometry of the forced launch (launch_fm_hot): LPR = row bytes / 16 lanes per
+Geometry of the forced launch (try_fm_hot): LPR = row bytes / 16 lanes per
 row, RPW = 64 / LPR rows per slot, U = 6 slots (4 at F > 6), RPI = RPW * U rows
 per wave-iteration, a quarter of ceil(B / (4 * RPI)) blocks of 4 waves; wave v
 takes the iterations at v * RPI + i * (waves * RPI).

@@ -44,6 +44,8 @@ def parse_args(dataname, factor, TopK, argv=None):
     p.add_argument("--result_file", default="../result.txt")
     p.add_argument("--deterministic", type=int, default=0,
                    help="1: bit-reproducible training steps (row-ordered sums)")
+    p.add_argument("--filter_seen", type=int, default=0, choices=(0, 1),
+                   help="1: HR / NDCG / PRE over top-K lists without each key's train positives")
     return p.parse_args(argv)
 
 
@@ -120,22 +122,27 @@ class AFM(ScoringModel):
                               float(self.weights["bias"]), Wt, b, p, P)
         return self._np_out(out)
 
-    def catalog_topk(self, q, begin, count, K):
+    def catalog_topk(self, q, begin, count, K, exclude=None):
         """Top-K of items [begin, begin+count) by the attention score of
         AFM.py:209-246 -> (scores, global item offsets) device tensors [B, K].
         With attention=0 the score is ``out`` of the row with column 1 replaced
         by the item (this library's definition: the reference's topk raises
-        KeyError('attention_W') there)."""
+        KeyError('attention_W') there).  ``exclude``: an ops.ExclusionLists, or a
+        positive_feedback-style dict key tuple -> set of table row ids, of the
+        rows every query leaves out (include/hhfm.h "Exclusion lists")."""
+        extra = {} if exclude is None else {"exclude": self._exclusion(q, exclude)}
         if not self.attention:
             return ops.afm_noatt_catalog_topk(
                 q, self.table, self.weights["feature_bias"].reshape(-1),
-                float(self.weights["bias"]), self._P(), self.n_user + begin, count, int(K), begin)
+                float(self.weights["bias"]), self._P(), self.n_user + begin, count, int(K), begin,
+                **extra)
         Wt, b, p, P = self._att()
         return ops.afm_catalog_topk(q, self.table, self.weights["feature_bias"].reshape(-1),
-                                    Wt, b, p, P, self.n_user + begin, count, int(K), begin)
+                                    Wt, b, p, P, self.n_user + begin, count, int(K), begin,
+                                    **extra)
 
-    def topk(self, A, tp):
-        _, ids = self.catalog_topk(self._idx(A), 0, self.n_item, tp)
+    def topk(self, A, tp, exclude=None):
+        _, ids = self.catalog_topk(self._idx(A), 0, self.n_item, tp, exclude=exclude)
         return ids.cpu().numpy()
 
     def _run_fetch(self, fetch, feed):

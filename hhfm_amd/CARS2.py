@@ -53,6 +53,8 @@ def parse_args(dataname, factor, Topk, argv=None):
     p.add_argument("--result_file", default="../result.txt")
     p.add_argument("--deterministic", type=int, default=0,
                    help="1: bit-reproducible training steps (not built for CARS2)")
+    p.add_argument("--filter_seen", type=int, default=0, choices=(0, 1),
+                   help="1: HR / NDCG / PRE over top-K lists without each key's train positives")
     return p.parse_args(argv)
 
 
@@ -169,22 +171,38 @@ class CARS2(ScoringModel):
         self._check()
         return self._np_out(out)
 
-    def catalog_topk(self, q, begin, count, K):
+    def _exclusion(self, q, exclude):
+        """``exclude`` of a topk call as ops.ExclusionLists (or None): the lists
+        themselves (rows of UI), or a dict (user id, context id) -> set of UI
+        rows, looked up with the query rows ``q`` [B, 2]."""
+        if exclude is None or isinstance(exclude, ops.ExclusionLists):
+            return exclude
+        if not isinstance(exclude, dict):
+            raise TypeError("exclude must be an ops.ExclusionLists or a dict key -> set of ids")
+        rows = q.cpu().numpy() if isinstance(q, torch.Tensor) else np.asarray(q)
+        return ops.exclusion_lists([exclude.get(tuple(r), ()) for r in rows.tolist()],
+                                   self.device)
+
+    def catalog_topk(self, q, begin, count, K, exclude=None):
         """Top-K of items [begin, begin+count) for queries ``q`` [B, 2] = (user
         id, context id) (CARS2.py:171-187) -> (scores, global item offsets)
-        device tensors [B, K]."""
+        device tensors [B, K].  ``exclude``: an ops.ExclusionLists of UI rows, or
+        a dict (user id, context id) -> set of UI rows, that every query leaves
+        out (include/hhfm.h "Exclusion lists")."""
+        extra = {} if exclude is None else {"exclude": self._exclusion(q, exclude)}
         out = ops.cars2_catalog_topk(q, self.table, self._prepared(), self.features_M, int(K),
-                                     self.n_user + begin, count, begin, status=self._status())
+                                     self.n_user + begin, count, begin, status=self._status(),
+                                     **extra)
         self._check()
         return out
 
-    def topk(self, feed, tp):
+    def topk(self, feed, tp, exclude=None):
         """``feed``: the reference's dict {'X': user ids [B], 'F1': context ids
-        [B]} (CARS2.py:332) or an array [B, 2]."""
+        [B]} (CARS2.py:332) or an array [B, 2]; ``exclude`` as in catalog_topk."""
         if isinstance(feed, dict):
             feed = np.stack([np.asarray(feed["X"]).reshape(-1),
                              np.asarray(feed["F1"]).reshape(-1)], axis=1)
-        _, ids = self.catalog_topk(self._idx(feed), 0, self.n_item, tp)
+        _, ids = self.catalog_topk(self._idx(feed), 0, self.n_item, tp, exclude=exclude)
         return ids.cpu().numpy()
 
     def _run_fetch(self, fetch, feed):
@@ -221,9 +239,14 @@ class _FullRows:
         rows = np.asarray(rows)
         return self._m.score_rows(np.column_stack([rows[:, 0], rows[:, 1], self._ctx(rows)]))
 
-    def topk(self, rows, tp):
+    def topk(self, rows, tp, exclude=None):
+        """``exclude``: an ops.ExclusionLists, or a positive_feedback-style dict
+        keyed by the full rows' columns but the item."""
         rows = np.asarray(rows)
-        return self._m.topk({"X": rows[:, 0], "F1": self._ctx(rows)}, tp)
+        if isinstance(exclude, dict):
+            exclude = ScoringModel._exclusion(self._m, rows, exclude)
+        extra = {} if exclude is None else {"exclude": exclude}
+        return self._m.topk({"X": rows[:, 0], "F1": self._ctx(rows)}, tp, **extra)
 
 
 class Train(harness.Train):
@@ -262,6 +285,9 @@ class Train(harness.Train):
 
     def evaluate_TopK(self, data1):
         return self._through_full_rows(super().evaluate_TopK, data1)
+
+    def evaluate_TopK_filtered(self, data1):
+        return self._through_full_rows(super().evaluate_TopK_filtered, data1)
 
     def context_ids(self, rows):
         return _context_ids(self.feature_inject, rows)

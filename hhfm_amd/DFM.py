@@ -41,6 +41,8 @@ def parse_args(dataname, factor, Topk, argv=None):
     p.add_argument("--result_file", default="../result.txt")
     p.add_argument("--deterministic", type=int, default=0,
                    help="1: bit-reproducible training steps (row-ordered sums)")
+    p.add_argument("--filter_seen", type=int, default=0, choices=(0, 1),
+                   help="1: HR / NDCG / PRE over top-K lists without each key's train positives")
     return p.parse_args(argv)
 
 
@@ -137,18 +139,22 @@ class DeepFM(ScoringModel):
                               dims, self.mlp_dtype, Wp, bp, head=self._head_arg())
         return self._np_out(out)
 
-    def catalog_topk(self, q, begin, count, K):
+    def catalog_topk(self, q, begin, count, K, exclude=None):
         """Top-K of items [begin, begin+count) by the DeepFM score of
         DFM.py:219-231 -> (scores, global item offsets) device tensors [B, K].
         The scores are the pre-sigmoid projection for every loss_type (the
-        ranking is the sigmoid's; item-shard merges stay exact)."""
+        ranking is the sigmoid's; item-shard merges stay exact).  ``exclude``:
+        an ops.ExclusionLists, or a positive_feedback-style dict key tuple ->
+        set of table row ids, of the rows every query leaves out (include/hhfm.h
+        "Exclusion lists")."""
         Wt, bs, dims, Wp, bp = self._prepared()
+        extra = {} if exclude is None else {"exclude": self._exclusion(q, exclude)}
         return ops.dfm_catalog_topk(q, self.table, self.weights["feature_bias"].reshape(-1),
                                     Wt, bs, dims, Wp, bp, 1, self.n_user + begin, count, int(K),
-                                    begin, head=self._head_arg())
+                                    begin, head=self._head_arg(), **extra)
 
-    def topk(self, A, tp):
-        _, ids = self.catalog_topk(self._idx(A), 0, self.n_item, tp)
+    def topk(self, A, tp, exclude=None):
+        _, ids = self.catalog_topk(self._idx(A), 0, self.n_item, tp, exclude=exclude)
         return ids.cpu().numpy()
 
     def _run_fetch(self, fetch, feed):

@@ -1407,15 +1407,14 @@ extern "C" int hhfm_afm_catalog_topk(const int32_t* qidx, int64_t B, int32_t F, 
                                   stream);
 }
 
-extern "C" int hhfm_afm_catalog_topk_ex(const int32_t* qidx, int64_t B, int32_t F,
-                                        const void* E, int64_t features_M, int32_t k,
-                                        int32_t dtype, const float* w, const float* Wt,
-                                        const float* att_b, const float* att_p, int32_t A,
-                                        const float* P, int32_t item_row_begin,
-                                        int32_t item_count, int32_t global_item_base, int32_t K,
-                                        int64_t max_cols, float* top_score, int32_t* top_idx,
-                                        int32_t plan, void* workspace, size_t ws_bytes,
-                                        void* stream) {
+// excl: the call's exclusion lists (hhfm_afm_catalog_topk_excl) or NULL
+static int afm_catalog_impl(const int32_t* qidx, int64_t B, int32_t F, const void* E,
+                            int64_t features_M, int32_t k, int32_t dtype, const float* w,
+                            const float* Wt, const float* att_b, const float* att_p, int32_t A,
+                            const float* P, int32_t item_row_begin, int32_t item_count,
+                            int32_t global_item_base, int32_t K, int64_t max_cols,
+                            float* top_score, int32_t* top_idx, int32_t plan, void* workspace,
+                            size_t ws_bytes, void* stream, const ExclLists* excl) {
   if (plan & ~HHFM_PLAN_ALL) return HHFM_EINVAL;
   if (B < 0 || F < 3 || F - 1 > kAfmMaxUF || k < 1 || k > kAfmMaxK || A < 1 ||
       features_M < 1 || max_cols < 1)
@@ -1425,6 +1424,7 @@ extern "C" int hhfm_afm_catalog_topk_ex(const int32_t* qidx, int64_t B, int32_t 
     return HHFM_EINVAL;
   if (K < 1 || K > item_count) return HHFM_EINVAL;
   if (K > 64) return HHFM_EUNSUPPORTED;
+  if (excl && !excl_args_ok(*excl, B, item_count, K)) return HHFM_EINVAL;
   if (!afm_cat_fused_ok(F, k, A, plan) && (k % 4 || A % 16))
     return HHFM_EUNSUPPORTED;
   if (B == 0) return HHFM_OK;
@@ -1557,6 +1557,9 @@ extern "C" int hhfm_afm_catalog_topk_ex(const int32_t* qidx, int64_t B, int32_t 
     }
     int64_t tblocks = (nq + 3) / 4;
     if (tblocks > 4096) tblocks = 4096;
+    if (excl)   // the lists are indexed by the call's query number; sc is this chunk's alone
+      launch_excl_mask_scores(ExclLists{excl->ptr + b0, excl->rows, 0}, nq, item_row_begin,
+                              item_count, sc, item_count, st);
     if (K <= 32)
       hipLaunchKernelGGL((topk_dense_kernel<32, 32>), dim3((unsigned)tblocks), dim3(256), 0, st, sc, nq,
                          item_count, (int64_t)item_count, K, global_item_base,
@@ -1567,4 +1570,37 @@ extern "C" int hhfm_afm_catalog_topk_ex(const int32_t* qidx, int64_t B, int32_t 
                          top_score + b0 * K, top_idx + b0 * K, nullptr);
   }
   return (int)hipGetLastError();
+}
+
+extern "C" int hhfm_afm_catalog_topk_ex(const int32_t* qidx, int64_t B, int32_t F,
+                                        const void* E, int64_t features_M, int32_t k,
+                                        int32_t dtype, const float* w, const float* Wt,
+                                        const float* att_b, const float* att_p, int32_t A,
+                                        const float* P, int32_t item_row_begin,
+                                        int32_t item_count, int32_t global_item_base, int32_t K,
+                                        int64_t max_cols, float* top_score, int32_t* top_idx,
+                                        int32_t plan, void* workspace, size_t ws_bytes,
+                                        void* stream) {
+  return afm_catalog_impl(qidx, B, F, E, features_M, k, dtype, w, Wt, att_b, att_p, A, P,
+                          item_row_begin, item_count, global_item_base, K, max_cols, top_score,
+                          top_idx, plan, workspace, ws_bytes, stream, nullptr);
+}
+
+// hhfm_afm_catalog_topk_ex over each query's non-listed items (include/hhfm.h
+// "Exclusion lists"): the same scores on the same route, the listed ones
+// masked in the chunk's score block, then the same dense select.
+extern "C" int hhfm_afm_catalog_topk_excl(const int32_t* qidx, int64_t B, int32_t F,
+                                          const void* E, int64_t features_M, int32_t k,
+                                          int32_t dtype, const float* w, const float* Wt,
+                                          const float* att_b, const float* att_p, int32_t A,
+                                          const float* P, int32_t item_row_begin,
+                                          int32_t item_count, int32_t global_item_base,
+                                          int32_t K, int64_t max_cols, float* top_score,
+                                          int32_t* top_idx, int32_t plan, void* workspace,
+                                          size_t ws_bytes, void* stream, const int64_t* excl_ptr,
+                                          const int32_t* excl_rows, int64_t max_excl) {
+  const ExclLists x{excl_ptr, excl_rows, max_excl};
+  return afm_catalog_impl(qidx, B, F, E, features_M, k, dtype, w, Wt, att_b, att_p, A, P,
+                          item_row_begin, item_count, global_item_base, K, max_cols, top_score,
+                          top_idx, plan, workspace, ws_bytes, stream, &x);
 }

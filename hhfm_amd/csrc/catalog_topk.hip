@@ -1264,14 +1264,6 @@ static Plan make_plan(int64_t B, int32_t N, int32_t k, int32_t K, int32_t plan, 
   return p;
 }
 
-// caller's exclusion lists (include/hhfm.h "Exclusion lists"); max_excl is
-// checked on the host and sizes nothing
-struct ExclLists {
-  const int64_t* ptr;
-  const int32_t* rows;
-  int64_t max_excl;
-};
-
 template <bool BF16, int KT, int KPAD, bool FM, bool EXCL = false>
 static void launch_main(const Plan& p, const float* H, const float* cst, int64_t B,
                         const char* E, int64_t item_row_begin, int32_t N,
@@ -1521,6 +1513,11 @@ static void launch_excl_mask(const ExclLists& x, int64_t B, int64_t irb, int32_t
                      n, shift, sc, ld);
 }
 
+void launch_excl_mask_scores(const ExclLists& x, int64_t B, int64_t item_row_begin, int32_t n,
+                             float* sc, int64_t ld, hipStream_t st) {
+  launch_excl_mask(x, B, item_row_begin, n, 0, sc, ld, st);
+}
+
 static void launch_merge(const float* in_s, const int32_t* in_i, int R, int64_t B,
                          int K, int64_t stride_r, int64_t stride_b, float* os,
                          int32_t* oi, hipStream_t st) {
@@ -1601,8 +1598,7 @@ static int catalog_topk_impl(
   if (K < 1 || K > item_count) return HHFM_EINVAL;
   if (K > 64) return HHFM_EUNSUPPORTED;
   // exclusion lists: K admissible items must remain whatever the lists hold
-  if (excl && (excl->max_excl < 0 || (int64_t)K + excl->max_excl > item_count)) return HHFM_EINVAL;
-  if (excl && B > 0 && !excl->ptr) return HHFM_EINVAL;
+  if (excl && !excl_args_ok(*excl, B, item_count, K)) return HHFM_EINVAL;
   const bool bf16 = dtype == HHFM_BF16;
   const int epc2 = bf16 ? 16 : 8;  // k per 16-B chunk pair (two lane halves)
   if (k % epc2) return HHFM_EUNSUPPORTED;
@@ -1900,6 +1896,42 @@ extern "C" int hhfm_afm_noatt_catalog_topk(
                            nullptr, &nq);
 }
 
+// The two calls above over each query's non-listed items (include/hhfm.h
+// "Exclusion lists"): the routes hhfm_catalog_topk_excl takes, behind the same
+// query kernels.  CARS2's lists hold rows of UI.
+extern "C" int hhfm_cars2_catalog_topk_excl(
+    const int32_t* q, int64_t B, const void* UI, int64_t n_ui, int32_t D, int32_t dtype,
+    const void* prepared, int64_t Mc, int32_t item_row_begin, int32_t item_count,
+    int32_t global_item_base, int32_t K, float* top_score, int32_t* top_idx, void* workspace,
+    size_t ws_bytes, int32_t plan, int32_t* status, void* stream, const int64_t* excl_ptr,
+    const int32_t* excl_rows, int64_t max_excl) {
+  if (Mc < 1 || D < 1) return HHFM_EINVAL;
+  if (B > 0 && !prepared) return HHFM_EINVAL;
+  const float* GA = reinterpret_cast<const float*>(prepared);
+  const Cars2Query cq{GA, GA + Mc * D, Mc};
+  const ExclLists x{excl_ptr, excl_rows, max_excl};
+  return catalog_topk_impl(q, B, 2, HHFM_MODE_FM, 0, 0, 0, 0, 0, UI, n_ui, D, dtype, nullptr,
+                           item_row_begin, item_count, global_item_base, K, top_score, top_idx,
+                           workspace, ws_bytes, plan, 0, status, stream, false, 0, &cq, nullptr,
+                           &x);
+}
+
+extern "C" int hhfm_afm_noatt_catalog_topk_excl(
+    const int32_t* qidx, int64_t B, int32_t F, const void* E, int64_t features_M, int32_t k,
+    int32_t dtype, const float* w, float w0, const float* P, int32_t item_row_begin,
+    int32_t item_count, int32_t global_item_base, int32_t K, float* top_score,
+    int32_t* top_idx, void* workspace, size_t ws_bytes, int32_t plan, int32_t* status,
+    void* stream, const int64_t* excl_ptr, const int32_t* excl_rows, int64_t max_excl) {
+  if (F < 2) return HHFM_EINVAL;
+  if (B > 0 && !P) return HHFM_EINVAL;
+  const NoAttQuery nq{P, w0};
+  const ExclLists x{excl_ptr, excl_rows, max_excl};
+  return catalog_topk_impl(qidx, B, F, HHFM_MODE_FM, kUserCol, 2, F, 0, 0, E, features_M, k,
+                           dtype, w, item_row_begin, item_count, global_item_base, K, top_score,
+                           top_idx, workspace, ws_bytes, plan, 0, status, stream, false, 0,
+                           nullptr, &nq, &x);
+}
+
 // make_plan as numbers, for the host-side tests of the workspace layout
 // (tests/test_workspace_contract.py; not part of include/hhfm.h): out[0..9] =
 // off_H, off_cst, off_thr, off_ps, off_pi, off_sc, off_seed_sc, off_seed_s,
@@ -1915,6 +1947,24 @@ extern "C" int hhfm_debug_catalog_plan(int64_t B, int32_t item_count, int32_t k,
                          (int64_t)p.total, p.dense, p.fS, p.S, p.rS[0], p.rS[1], p.seed_n};
   for (int i = 0; i < 16; ++i) out[i] = v[i];
   return HHFM_OK;
+}
+
+// The alternative hhfm_topk_dense_excl is measured against
+// (scripts/topk_excl_models_ab.py; not part of include/hhfm.h): excl_mask_kernel
+// on the caller's matrix — which it WRITES — then the plain dense select.
+extern "C" int hhfm_debug_mask_then_select(float* scores, int64_t B, int32_t N, int64_t ld,
+                                           int32_t K, int32_t global_item_base, float* top_score,
+                                           int32_t* top_idx, int32_t plan, void* stream,
+                                           int32_t item_row_begin, const int64_t* excl_ptr,
+                                           const int32_t* excl_rows) {
+  if (B < 1 || N < 1 || ld < N || K < 1 || K > N || K > 64 || (plan & ~HHFM_PLAN_ALL))
+    return HHFM_EINVAL;
+  if (!scores || !top_score || !top_idx || !excl_ptr) return HHFM_EINVAL;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  launch_excl_mask(ExclLists{excl_ptr, excl_rows, 0}, B, item_row_begin, N, 0, scores, ld, st);
+  launch_topk_dense(scores, B, N, ld, K, global_item_base, top_score, top_idx, st,
+                    (plan & HHFM_PLAN_ONE_WAVE) != 0);
+  return (int)hipGetLastError();
 }
 
 #if HHFM_FUSED_TIMING

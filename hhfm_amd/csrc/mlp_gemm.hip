@@ -539,7 +539,8 @@ static int dfm_catalog_run(const int32_t* qidx, int64_t B, int32_t F, int32_t it
                            int32_t item_count, int32_t global_item_base, int32_t K,
                            int64_t chunk_rows, float* top_score, int32_t* top_idx,
                            void* workspace, size_t ws_bytes, int proj_mode, int32_t plan,
-                           void* stream, bool deep_only = false) {
+                           void* stream, bool deep_only = false,
+                           const ExclLists* excl = nullptr) {
   int rc = dfm_check(B, F, k, dtype, nlayers, layer_dims, mlp_dtype);
   if (rc) return rc;
   if (item_col < 0 || item_col >= F || item_count < 1 || item_row_begin < 0 ||
@@ -547,6 +548,7 @@ static int dfm_catalog_run(const int32_t* qidx, int64_t B, int32_t F, int32_t it
     return HHFM_EINVAL;
   if (K < 1 || K > item_count) return HHFM_EINVAL;
   if (K > 64) return HHFM_EUNSUPPORTED;
+  if (excl && !excl_args_ok(*excl, B, item_count, K)) return HHFM_EINVAL;
   if (B == 0) return HHFM_OK;
   if (!qidx || !E || !w || !Wt || !bias || !Wp || !top_score || !top_idx) return HHFM_EINVAL;
   const int64_t qc = dfm_cat_qchunk(B, item_count, chunk_rows);
@@ -596,6 +598,9 @@ static int dfm_catalog_run(const int32_t* qidx, int64_t B, int32_t F, int32_t it
                           bias, mlp_dtype, Wp, bp, sc, ws, p, proj, nullptr, plan, &pairs_ready,
                           st);
     if (rc) return rc;
+    if (excl)   // the lists are indexed by the call's query number; sc is this chunk's alone
+      launch_excl_mask_scores(ExclLists{excl->ptr + b0, excl->rows, 0}, nb, item_row_begin,
+                              item_count, sc, item_count, st);
     launch_topk_dense(sc, nb, item_count, item_count, K, global_item_base, top_score + b0 * K,
                       top_idx + b0 * K, st, (plan & HHFM_PLAN_ONE_WAVE) != 0);
   }
@@ -643,7 +648,8 @@ static int dfm_catalog_fm(const int32_t* qidx, int64_t B, int32_t F, int32_t ite
                           const float* w, const float* Wp, float bp, int32_t item_row_begin,
                           int32_t item_count, int32_t global_item_base, int32_t K,
                           int64_t chunk_rows, float* top_score, int32_t* top_idx,
-                          void* workspace, size_t ws_bytes, int32_t plan, void* stream) {
+                          void* workspace, size_t ws_bytes, int32_t plan, void* stream,
+                          const ExclLists* excl = nullptr) {
   int rc = dfm_fm_head_check(B, F, k, dtype, features_M);
   if (rc) return rc;
   if (item_col < 0 || item_col >= F || item_count < 1 || item_row_begin < 0 ||
@@ -651,6 +657,7 @@ static int dfm_catalog_fm(const int32_t* qidx, int64_t B, int32_t F, int32_t ite
     return HHFM_EINVAL;
   if (K < 1 || K > item_count) return HHFM_EINVAL;
   if (K > 64) return HHFM_EUNSUPPORTED;
+  if (excl && !excl_args_ok(*excl, B, item_count, K)) return HHFM_EINVAL;
   if (B == 0) return HHFM_OK;
   if (!qidx || !E || !w || !Wp || !top_score || !top_idx) return HHFM_EINVAL;
   const int64_t qc = dfm_cat_qchunk(B, item_count, chunk_rows);
@@ -670,6 +677,9 @@ static int dfm_catalog_fm(const int32_t* qidx, int64_t B, int32_t F, int32_t ite
                        nb, F, item_col, item_row_begin, item_count, rbuf);
     dfm_fm_base_launch(rbuf, nrows, F, E, features_M, k, dtype == HHFM_BF16, w, Wp, bp, sc,
                        HHFM_PLAN_DEFAULT, st);
+    if (excl)   // the lists are indexed by the call's query number; sc is this chunk's alone
+      launch_excl_mask_scores(ExclLists{excl->ptr + b0, excl->rows, 0}, nb, item_row_begin,
+                              item_count, sc, item_count, st);
     launch_topk_dense(sc, nb, item_count, item_count, K, global_item_base, top_score + b0 * K,
                       top_idx + b0 * K, st, (plan & HHFM_PLAN_ONE_WAVE) != 0);
   }
@@ -696,6 +706,29 @@ extern "C" int hhfm_dfm_catalog_topk_head(
                          ws_bytes, proj_mode, plan, stream, !head_full(head));
 }
 
+// hhfm_dfm_catalog_topk_head over each query's non-listed items (include/hhfm.h
+// "Exclusion lists"): the same scores, the listed ones masked in the chunk's
+// score block, then the same dense select.
+extern "C" int hhfm_dfm_catalog_topk_excl(
+    const int32_t* qidx, int64_t B, int32_t F, int32_t item_col, const void* E,
+    int64_t features_M, int32_t k, int32_t dtype, const float* w, int32_t nlayers,
+    const int32_t* layer_dims, const void* const* Wt, const float* const* bias,
+    int32_t mlp_dtype, const float* Wp, float bp, int32_t item_row_begin, int32_t item_count,
+    int32_t global_item_base, int32_t K, int64_t chunk_rows, float* top_score, int32_t* top_idx,
+    int32_t proj_mode, int32_t plan, void* workspace, size_t ws_bytes, void* stream,
+    int32_t head, const int64_t* excl_ptr, const int32_t* excl_rows, int64_t max_excl) {
+  if (!head_ok(head) || !proj_mode_ok(proj_mode) || !plan_ok(plan)) return HHFM_EINVAL;
+  const ExclLists x{excl_ptr, excl_rows, max_excl};
+  if (!(head & HHFM_DFM_HEAD_DEEP))
+    return dfm_catalog_fm(qidx, B, F, item_col, E, features_M, k, dtype, w, Wp, bp,
+                          item_row_begin, item_count, global_item_base, K, chunk_rows, top_score,
+                          top_idx, workspace, ws_bytes, plan, stream, &x);
+  return dfm_catalog_run(qidx, B, F, item_col, E, features_M, k, dtype, w, nlayers, layer_dims,
+                         Wt, bias, mlp_dtype, Wp, bp, item_row_begin, item_count,
+                         global_item_base, K, chunk_rows, top_score, top_idx, workspace,
+                         ws_bytes, proj_mode, plan, stream, !head_full(head), &x);
+}
+
 extern "C" int hhfm_topk_dense(const float* scores, int64_t B, int32_t N, int64_t ld, int32_t K,
                                int32_t global_item_base, float* top_score, int32_t* top_idx,
                                void* stream) {
@@ -717,5 +750,24 @@ extern "C" int hhfm_topk_dense_ex(const float* scores, int64_t B, int32_t N, int
   if (!scores || !top_score || !top_idx) return HHFM_EINVAL;
   launch_topk_dense(scores, B, N, ld, K, global_item_base, top_score, top_idx,
                     reinterpret_cast<hipStream_t>(stream), (plan & HHFM_PLAN_ONE_WAVE) != 0);
+  return (int)hipGetLastError();
+}
+
+// hhfm_topk_dense_ex over each query's non-listed columns (include/hhfm.h
+// "Exclusion lists"); column i is table row item_row_begin + i.  S is not
+// written.
+extern "C" int hhfm_topk_dense_excl(const float* scores, int64_t B, int32_t N, int64_t ld,
+                                    int32_t K, int32_t global_item_base, float* top_score,
+                                    int32_t* top_idx, int32_t plan, void* stream,
+                                    int32_t item_row_begin, const int64_t* excl_ptr,
+                                    const int32_t* excl_rows, int64_t max_excl) {
+  if (!plan_ok(plan) || B < 0 || N < 1 || ld < N || K < 1 || K > N) return HHFM_EINVAL;
+  if (K > 64) return HHFM_EUNSUPPORTED;
+  if (!excl_args_ok(ExclLists{excl_ptr, excl_rows, max_excl}, B, N, K)) return HHFM_EINVAL;
+  if (B == 0) return HHFM_OK;
+  if (!scores || !top_score || !top_idx) return HHFM_EINVAL;
+  launch_topk_dense_excl(scores, B, N, ld, K, global_item_base, top_score, top_idx,
+                         reinterpret_cast<hipStream_t>(stream),
+                         (plan & HHFM_PLAN_ONE_WAVE) != 0, excl_ptr, excl_rows, item_row_begin);
   return (int)hipGetLastError();
 }

@@ -17,6 +17,13 @@
 // catalog_topk.hip: make_plan as numbers (a test hook, not in include/hhfm.h)
 extern "C" int hhfm_debug_catalog_plan(int64_t B, int32_t item_count, int32_t k, int32_t K,
                                        int32_t plan, int32_t dtype, int64_t* out);
+// catalog_topk.hip: excl_mask_kernel + the plain dense select on a caller's
+// matrix, which it writes (a measurement hook, not in include/hhfm.h)
+extern "C" int hhfm_debug_mask_then_select(float* scores, int64_t B, int32_t N, int64_t ld,
+                                           int32_t K, int32_t global_item_base, float* top_score,
+                                           int32_t* top_idx, int32_t plan, void* stream,
+                                           int32_t item_row_begin, const int64_t* excl_ptr,
+                                           const int32_t* excl_rows);
 
 namespace py = pybind11;
 using uptr = std::uintptr_t;
@@ -342,6 +349,18 @@ PYBIND11_MODULE(_hhfm, m) {
     for (int i = 0; i < 16; ++i) d[names[i]] = v[i];
     return d;
   });
+
+  m.def("debug_mask_then_select",
+        [](uptr scores, int64_t B, int N, int64_t ld, int K, int base, uptr top_score,
+           uptr top_idx, int plan, uptr stream, int item_row_begin, uptr excl_ptr,
+           uptr excl_rows) {
+          check(hhfm_debug_mask_then_select(P<float>(scores), B, N, ld, K, base,
+                                            P<float>(top_score), P<int32_t>(top_idx), plan,
+                                            P<void>(stream), item_row_begin,
+                                            P<const int64_t>(excl_ptr),
+                                            P<const int32_t>(excl_rows)),
+                "hhfm_debug_mask_then_select");
+        });
 
   m.def("catalog_topk_workspace",
         [](int64_t B, int item_count, int k, int K) {
@@ -1132,6 +1151,108 @@ PYBIND11_MODULE(_hhfm, m) {
                                     P<void>(stream));
           }
           check(rc, "hhfm_topk_dense_ex");
+        });
+
+  // exclusion lists of the other catalogs (include/hhfm.h "Exclusion lists"):
+  // the plain call's arguments, then excl_ptr, excl_rows, max_excl
+  m.def("topk_dense_excl",
+        [](uptr scores, int64_t B, int N, int64_t ld, int K, int base, uptr top_score,
+           uptr top_idx, int plan, uptr stream, int item_row_begin, uptr excl_ptr,
+           uptr excl_rows, int64_t max_excl) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_topk_dense_excl(P<const float>(scores), B, N, ld, K, base,
+                                      P<float>(top_score), P<int32_t>(top_idx), plan,
+                                      P<void>(stream), item_row_begin,
+                                      P<const int64_t>(excl_ptr), P<const int32_t>(excl_rows),
+                                      max_excl);
+          }
+          check(rc, "hhfm_topk_dense_excl");
+        });
+
+  m.def("cars2_catalog_topk_excl",
+        [](uptr q, int64_t B, uptr UI, int64_t n_ui, int D, int dtype, uptr prepared, int64_t Mc,
+           int item_row_begin, int item_count, int global_item_base, int K, uptr top_score,
+           uptr top_idx, uptr ws, size_t ws_bytes, int plan, uptr status, uptr stream,
+           uptr excl_ptr, uptr excl_rows, int64_t max_excl) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_cars2_catalog_topk_excl(
+                P<const int32_t>(q), B, P<const void>(UI), n_ui, D, dtype,
+                P<const void>(prepared), Mc, item_row_begin, item_count, global_item_base, K,
+                P<float>(top_score), P<int32_t>(top_idx), P<void>(ws), ws_bytes, plan,
+                P<int32_t>(status), P<void>(stream), P<const int64_t>(excl_ptr),
+                P<const int32_t>(excl_rows), max_excl);
+          }
+          check(rc, "hhfm_cars2_catalog_topk_excl");
+        });
+
+  m.def("afm_noatt_catalog_topk_excl",
+        [](uptr qidx, int64_t B, int F, uptr E, int64_t M, int k, int dtype, uptr w, float w0,
+           uptr Pv, int item_row_begin, int item_count, int global_item_base, int K,
+           uptr top_score, uptr top_idx, uptr ws, size_t ws_bytes, int plan, uptr status,
+           uptr stream, uptr excl_ptr, uptr excl_rows, int64_t max_excl) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_afm_noatt_catalog_topk_excl(
+                P<const int32_t>(qidx), B, F, P<const void>(E), M, k, dtype, P<const float>(w),
+                w0, P<const float>(Pv), item_row_begin, item_count, global_item_base, K,
+                P<float>(top_score), P<int32_t>(top_idx), P<void>(ws), ws_bytes, plan,
+                P<int32_t>(status), P<void>(stream), P<const int64_t>(excl_ptr),
+                P<const int32_t>(excl_rows), max_excl);
+          }
+          check(rc, "hhfm_afm_noatt_catalog_topk_excl");
+        });
+
+  m.def("afm_catalog_topk_excl",
+        [](uptr q, int64_t B, int F, uptr E, int64_t M, int k, int dtype, uptr w, uptr Wt,
+           uptr ab, uptr ap, int A, uptr Pv, int irb, int cnt, int gbase, int K,
+           int64_t max_cols, uptr ts, uptr ti, int plan, uptr ws, size_t ws_bytes, uptr stream,
+           uptr excl_ptr, uptr excl_rows, int64_t max_excl) {
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_afm_catalog_topk_excl(
+                P<const int32_t>(q), B, F, P<const void>(E), M, k, dtype, P<const float>(w),
+                P<const float>(Wt), P<const float>(ab), P<const float>(ap), A,
+                P<const float>(Pv), irb, cnt, gbase, K, max_cols, P<float>(ts),
+                P<int32_t>(ti), plan, P<void>(ws), ws_bytes, P<void>(stream),
+                P<const int64_t>(excl_ptr), P<const int32_t>(excl_rows), max_excl);
+          }
+          check(rc, "hhfm_afm_catalog_topk_excl");
+        });
+
+  m.def("dfm_catalog_topk_excl",
+        [](uptr qidx, int64_t B, int F, int item_col, uptr E, int64_t M, int k, int dtype,
+           uptr w, std::vector<int32_t> dims, std::vector<uptr> Wt, std::vector<uptr> bias,
+           int mlp_dtype, uptr Wp, float bp, int item_row_begin, int item_count,
+           int global_item_base, int K, int64_t chunk_rows, uptr top_score, uptr top_idx,
+           int proj_mode, int plan, uptr ws, size_t ws_bytes, uptr stream, int head,
+           uptr excl_ptr, uptr excl_rows, int64_t max_excl) {
+          if (Wt.size() != dims.size() || bias.size() != dims.size())
+            throw py::value_error("dims, Wt and bias must have the same length");
+          std::vector<const void*> W(Wt.size());
+          std::vector<const float*> b(bias.size());
+          for (size_t i = 0; i < W.size(); ++i) {
+            W[i] = P<const void>(Wt[i]);
+            b[i] = P<const float>(bias[i]);
+          }
+          int rc;
+          {
+            py::gil_scoped_release nogil;
+            rc = hhfm_dfm_catalog_topk_excl(
+                P<const int32_t>(qidx), B, F, item_col, P<const void>(E), M, k, dtype,
+                P<const float>(w), (int)dims.size(), dims.empty() ? nullptr : dims.data(),
+                W.empty() ? nullptr : W.data(), b.empty() ? nullptr : b.data(), mlp_dtype,
+                P<const float>(Wp), bp, item_row_begin, item_count, global_item_base, K,
+                chunk_rows, P<float>(top_score), P<int32_t>(top_idx), proj_mode, plan,
+                P<void>(ws), ws_bytes, P<void>(stream), head, P<const int64_t>(excl_ptr),
+                P<const int32_t>(excl_rows), max_excl);
+          }
+          check(rc, "hhfm_dfm_catalog_topk_excl");
         });
 
   m.def("topk_merge_host",

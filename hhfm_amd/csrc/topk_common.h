@@ -125,15 +125,22 @@ HHFM_DEV void merge_lists(float& as, int32_t& ai, float bs, int32_t bi) {
 // cs / ci: 64 LDS slots private to the wave.  The rare heavy-tie path
 // re-reads src in a rolled loop (keeps the kernel's code small: a fully
 // unrolled fallback made these kernels instruction-fetch bound).
-template <int KPAD, int NV>
+// EXCL (the exclusion form below): bit j of ex says that this lane's v[j] is a
+// listed column.  Such a score takes part in nothing: not in the lane maxima
+// that seed the threshold (the K lanes behind it must hold admissible scores),
+// not in the candidates, and not in the heavy-tie path's second read of src.
+template <int KPAD, int NV, bool EXCL = false>
 HHFM_DEV void topk_fold_chunk(const float (&v)[NV], const float* src, int32_t cb, int32_t n,
                               int K, float& ls, int32_t& li, float& thr, float* cs_lds,
-                              int32_t* ci_lds) {
+                              int32_t* ci_lds, uint32_t ex = 0u) {
+  static_assert(!EXCL || NV <= 32, "one bit of ex per score of the lane");
   const int l = lane_id();
+  const auto out = [&](int j) { return EXCL && ((ex >> j) & 1u); };
   if (thr == kNegInf) {   // list not full yet: K-th best lane maximum bounds the K-th score
-    float mx = v[0];
+    float mx = out(0) ? kNegInf : v[0];
 #pragma unroll
-    for (int j = 1; j < NV; ++j) mx = fmaxf(mx, cb + j * kWave + l < n ? v[j] : kNegInf);
+    for (int j = 1; j < NV; ++j)
+      mx = fmaxf(mx, (cb + j * kWave + l < n && !out(j)) ? v[j] : kNegInf);
     if (cb + l >= n) mx = kNegInf;
     int32_t dummy = l;
     bitonic_sort_desc<64>(mx, dummy);
@@ -142,13 +149,14 @@ HHFM_DEV void topk_fold_chunk(const float (&v)[NV], const float* src, int32_t cb
   // cheap test first: most chunks after the first hold few or no candidates
   int mine = 0;
 #pragma unroll
-  for (int j = 0; j < NV; ++j) mine += (cb + j * kWave + l < n && v[j] >= thr) ? 1 : 0;
+  for (int j = 0; j < NV; ++j)
+    mine += (cb + j * kWave + l < n && !out(j) && v[j] >= thr) ? 1 : 0;
   if (__ballot(mine > 0) == 0) return;
   int total = 0;
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
     const int32_t i = cb + j * kWave + l;
-    const bool pass = i < n && v[j] >= thr;
+    const bool pass = i < n && !out(j) && v[j] >= thr;
     const uint64_t m = __ballot(pass);
     if (pass) {
       const int pos = total + (int)__builtin_amdgcn_mbcnt_hi(
@@ -179,7 +187,7 @@ HHFM_DEV void topk_fold_chunk(const float (&v)[NV], const float* src, int32_t cb
     for (int j = 0; j < NV; ++j) {
       const int32_t i = cb + j * kWave + l;
       const float x = i < n ? src[j * kWave + l] : kNegInf;
-      const bool pass = i < n && x >= thr;
+      const bool pass = i < n && !out(j) && x >= thr;
       if (__ballot(pass) == 0) continue;
       float cs = pass ? x : kNegInf;
       int32_t ci = pass ? i : kNoIdx;
@@ -298,6 +306,207 @@ __global__ __launch_bounds__(256) void topk_dense_split_kernel(const float* __re
   }
 }
 
+// ---------------------------------------------------------------------------
+// exclusion form of the dense select (include/hhfm.h "Exclusion lists")
+//
+// The same two kernels over the columns that the query's list does not name:
+// excl_rows[excl_ptr[b] .. excl_ptr[b + 1]) holds table rows, strictly
+// ascending, and column i of S is table row item_row_begin + i.  S is only
+// read.  The wave that folds columns [lo, hi) keeps a cursor into the list —
+// the first entry not below lo, found by one binary search — and, per chunk of
+// NV·64 scores, moves it over the chunk's entries while their bits go into NV
+// 64-bit LDS words of the wave (word j bit l = column cb + 64 j + l).  Every
+// lane then reads its half of the NV words (two addresses for the whole wave,
+// each a broadcast: no bank conflict) and keeps its own bit of each in a
+// register, which is what topk_fold_chunk<…, EXCL> consults.  A chunk without
+// a listed column — nearly all of them — costs one compare and takes the plain
+// fold.  List entries are compared and turned into
+// a bounded LDS bit position; none is ever used as an index into S or a table,
+// so a negative row, one outside the shard or past the table changes nothing.
+// ---------------------------------------------------------------------------
+// wave-uniform: first x in [x0, x1) with rows[x] - irb >= lo
+HHFM_DEV int64_t excl_lower_bound(const int32_t* __restrict__ rows, int64_t x0, int64_t x1,
+                                  int64_t irb, int32_t lo) {
+  if (x0 >= x1 || (int64_t)rows[x0] - irb >= lo) return x0;
+  int64_t a = x0 + 1, b = x1;   // rows[a - 1] lies below lo
+  while (a < b) {
+    const int64_t mid = a + ((b - a) >> 1);
+    if ((int64_t)rows[mid] - irb < lo) a = mid + 1; else b = mid;
+  }
+  return a;
+}
+
+// LDS traffic of one wave, ordered for the compiler as well as the hardware
+HHFM_DEV void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// This lane's listed-column bits of the chunk [cb, cend) (cend - cb <= NV·64):
+// bit j <=> column cb + 64 j + lane is listed.  xc: the wave's cursor, moved
+// past every entry below cend.  xm: NV words private to the wave.  any (the
+// same in every lane): the chunk holds an entry of the list at all.
+template <int NV>
+HHFM_DEV uint32_t excl_chunk_bits(const int32_t* __restrict__ rows, int64_t& xc, int64_t xe,
+                                  int64_t irb, int32_t cb, int32_t cend,
+                                  unsigned long long* xm, bool& any) {
+  static_assert(NV <= 32, "one bit per score of the lane");
+  any = xc < xe && (int64_t)rows[xc] - irb < cend;
+  if (!any) return 0u;
+  const int l = lane_id();
+  if (l < NV) xm[l] = 0ull;
+  wave_lds_sync();
+  for (;;) {
+    const int64_t x = xc + l;
+    const int64_t o = x < xe ? (int64_t)rows[x] - irb : (int64_t)cend;
+    const bool in = o < cend;
+    if (in && o >= cb) atomicOr(&xm[(o - cb) >> 6], 1ull << ((o - cb) & 63));
+    const int c = __popcll(__ballot(in));
+    xc += c;
+    if (c < kWave) break;
+  }
+  wave_lds_sync();
+  // the lane's half of every word: two addresses per wave, each a broadcast
+  const uint32_t* xh = reinterpret_cast<const uint32_t*>(xm) + (l >> 5);
+  uint32_t ex = 0u;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) ex |= ((xh[2 * j] >> (l & 31)) & 1u) << j;
+  wave_lds_sync();   // the next chunk with entries clears the words
+  return ex;
+}
+
+// The wave's cursor over one query's list for the columns [lo, hi).  The
+// list is first touched by the first chunk's step, behind that chunk's score
+// loads: the reads of excl_ptr and of the first entries then wait beside the
+// scores, not in front of them.
+struct ExclCursor {
+  const int32_t* rows;
+  int64_t x0, xc, xe, irb;
+  bool armed;
+};
+
+// Fold one chunk whose scores v are loaded (or on their way): a chunk without
+// a listed column — the common one — takes the plain fold.
+template <int KPAD, int NV>
+HHFM_DEV void topk_fold_chunk_excl(const float (&v)[NV], const float* src, int32_t cb, int32_t n,
+                                   int32_t lo, int K, float& ls, int32_t& li, float& thr,
+                                   float* cs_lds, int32_t* ci_lds, unsigned long long* xm,
+                                   ExclCursor& c) {
+  if (!c.armed) {
+    c.armed = true;
+    c.xc = excl_lower_bound(c.rows, c.x0, c.xe, c.irb, lo);
+  }
+  const int32_t cend = cb + NV * kWave < n ? cb + NV * kWave : n;
+  bool any;
+  const uint32_t ex = excl_chunk_bits<NV>(c.rows, c.xc, c.xe, c.irb, cb, cend, xm, any);
+  if (any)
+    topk_fold_chunk<KPAD, NV, true>(v, src, cb, n, K, ls, li, thr, cs_lds, ci_lds, ex);
+  else
+    topk_fold_chunk<KPAD, NV>(v, src, cb, n, K, ls, li, thr, cs_lds, ci_lds);
+}
+
+template <int KPAD, int NV>
+__global__ __launch_bounds__(256) void topk_dense_excl_kernel(
+    const float* __restrict__ S, int64_t B, int32_t N, int64_t lds, int K, int32_t base,
+    float* __restrict__ out_s, int32_t* __restrict__ out_i,
+    const int64_t* __restrict__ excl_ptr, const int32_t* __restrict__ excl_rows, int64_t irb) {
+  __shared__ float cand_s[4][kWave];
+  __shared__ int32_t cand_i[4][kWave];
+  __shared__ unsigned long long xmask[4][NV];
+  const int l = lane_id(), wv = (threadIdx.x >> 6) & 3;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
+  const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) / kWave;
+  for (int64_t b = wave; b < B; b += nwave) {
+    const float* row = S + b * lds;
+    float ls = kNegInf;
+    int32_t li = kNoIdx;
+    float thr = kNegInf;
+    ExclCursor c{excl_rows, 0, 0, 0, irb, false};
+    if (excl_rows) {
+      c.x0 = excl_ptr[b];
+      c.xe = excl_ptr[b + 1];
+    }
+    for (int32_t cb = 0; cb < N; cb += NV * kWave) {
+      float v[NV];
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        const int32_t i = cb + j * kWave + l;
+        v[j] = i < N ? (HHFM_TOPK_NT ? __builtin_nontemporal_load(row + i) : row[i]) : kNegInf;
+      }
+      topk_fold_chunk_excl<KPAD, NV>(v, row + cb, cb, N, 0, K, ls, li, thr, cand_s[wv],
+                                     cand_i[wv], xmask[wv], c);
+    }
+    if (l < K) {
+      out_s[b * K + l] = ls;
+      out_i[b * K + l] = li == kNoIdx ? kNoIdx : li + base;
+    }
+  }
+}
+
+// WPQ waves per query: each wave's cursor starts at the first entry of its own
+// span; a span whose columns are all listed contributes an empty list, which
+// merge_lists passes over (-inf / kNoIdx rank behind everything).
+template <int KPAD, int NV, int WPQ>
+__global__ __launch_bounds__(256) void topk_dense_split_excl_kernel(
+    const float* __restrict__ S, int64_t B, int32_t N, int64_t lds, int K, int32_t base,
+    float* __restrict__ out_s, int32_t* __restrict__ out_i,
+    const int64_t* __restrict__ excl_ptr, const int32_t* __restrict__ excl_rows, int64_t irb) {
+  constexpr int QB = 4 / WPQ;   // queries per workgroup
+  __shared__ float cand_s[4][kWave];
+  __shared__ int32_t cand_i[4][kWave];
+  __shared__ float ms[4][KPAD];
+  __shared__ int32_t mi[4][KPAD];
+  __shared__ unsigned long long xmask[4][NV];
+  const int l = lane_id(), wv = (threadIdx.x >> 6) & 3;
+  const int qw = wv / WPQ, part = wv - qw * WPQ;
+  const int32_t span = (((N + WPQ - 1) / WPQ) + kWave - 1) / kWave * kWave;
+  const int32_t lo = part * span < N ? part * span : N;
+  const int32_t hi = lo + span < N ? lo + span : N;
+  for (int64_t b0 = (int64_t)blockIdx.x * QB; b0 < B; b0 += (int64_t)gridDim.x * QB) {
+    const int64_t b = b0 + qw;
+    float ls = kNegInf;
+    int32_t li = kNoIdx;
+    if (b < B) {
+      const float* row = S + b * lds;
+      float thr = kNegInf;
+      ExclCursor c{excl_rows, 0, 0, 0, irb, false};
+      if (excl_rows && lo < hi) {
+        c.x0 = excl_ptr[b];
+        c.xe = excl_ptr[b + 1];
+      }
+      for (int32_t cb = lo; cb < hi; cb += NV * kWave) {
+        float v[NV];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+          const int32_t i = cb + j * kWave + l;
+          v[j] = i < hi ? (HHFM_TOPK_NT ? __builtin_nontemporal_load(row + i) : row[i]) : kNegInf;
+        }
+        topk_fold_chunk_excl<KPAD, NV>(v, row + cb, cb, hi, lo, K, ls, li, thr, cand_s[wv],
+                                       cand_i[wv], xmask[wv], c);
+      }
+    }
+    if (l < KPAD) {
+      ms[wv][l] = ls;
+      mi[wv][l] = li;
+    }
+    __syncthreads();
+    if (part == 0 && b < B) {
+#pragma unroll
+      for (int p = 1; p < WPQ; ++p) {
+        const float bs = l < KPAD ? ms[wv + p][l] : kNegInf;
+        const int32_t bi = l < KPAD ? mi[wv + p][l] : kNoIdx;
+        merge_lists<KPAD>(ls, li, bs, bi);
+        if (l >= KPAD) { ls = kNegInf; li = kNoIdx; }
+      }
+      if (l < K) {
+        out_s[b * K + l] = ls;
+        out_i[b * K + l] = li == kNoIdx ? kNoIdx : li + base;
+      }
+    }
+    __syncthreads();   // ms / mi are rewritten by the next query group
+  }
+}
+
 // waves per query: 4 for <= 1,024 queries of >= 1,024 items (each folds a
 // 64-aligned quarter, the first merges); one_wave (HHFM_PLAN_ONE_WAVE) keeps
 // one wave per query at every size
@@ -335,6 +544,62 @@ static inline void launch_topk_dense(const float* S, int64_t B, int32_t N, int64
   else
     hipLaunchKernelGGL((topk_dense_kernel<64, HHFM_TOPK_NV>), dim3((int)blocks), dim3(256), 0, st, S, B, N, lds,
                        K, base, os, oi, kth);
+}
+
+// caller's exclusion lists (include/hhfm.h "Exclusion lists"); max_excl is
+// checked on the host and sizes nothing
+struct ExclLists {
+  const int64_t* ptr;
+  const int32_t* rows;
+  int64_t max_excl;
+};
+
+// K admissible items must remain whatever the lists hold; decided before
+// anything is launched
+static inline bool excl_args_ok(const ExclLists& x, int64_t B, int32_t N, int32_t K) {
+  if (x.max_excl < 0 || (int64_t)K + x.max_excl > N) return false;
+  return !(B > 0 && !x.ptr);
+}
+
+// excl_mask_kernel (catalog_topk.hip) on a score matrix: -FLT_MAX at every
+// listed column of the range, for a plain dense select to follow.  The AFM and
+// DeepFM catalogs take this route on their own score block, which each query
+// chunk rewrites: it measured faster than the select's exclusion form below
+// (DESIGN.md §K2 "Exclusion lists").
+void launch_excl_mask_scores(const ExclLists& x, int64_t B, int64_t item_row_begin, int32_t n,
+                             float* sc, int64_t ld, hipStream_t st);
+
+// launch_topk_dense over each query's non-listed columns: the same routing by
+// topk_dense_wpq, the exclusion kernels.  xrows NULL: every list is empty.
+static inline void launch_topk_dense_excl(const float* S, int64_t B, int32_t N, int64_t lds,
+                                          int K, int32_t base, float* os, int32_t* oi,
+                                          hipStream_t st, bool one_wave, const int64_t* xptr,
+                                          const int32_t* xrows, int64_t item_row_begin) {
+  const int wpq = topk_dense_wpq(B, N, one_wave);
+  if (wpq > 1) {
+    const int qb = 4 / wpq;
+    int64_t blocks = (B + qb - 1) / qb;
+    if (blocks > 8192) blocks = 8192;
+#define HHFM_TOPK_SPLIT_X(KP, W)                                                                 \
+  hipLaunchKernelGGL((topk_dense_split_excl_kernel<KP, HHFM_TOPK_NV, W>), dim3((int)blocks),     \
+                     dim3(256), 0, st, S, B, N, lds, K, base, os, oi, xptr, xrows, item_row_begin)
+    if (K <= 32) {
+      if (wpq == 4) HHFM_TOPK_SPLIT_X(32, 4); else HHFM_TOPK_SPLIT_X(32, 2);
+    } else {
+      if (wpq == 4) HHFM_TOPK_SPLIT_X(64, 4); else HHFM_TOPK_SPLIT_X(64, 2);
+    }
+#undef HHFM_TOPK_SPLIT_X
+    return;
+  }
+  int64_t blocks = (B + 3) / 4;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks < 1) blocks = 1;
+  if (K <= 32)
+    hipLaunchKernelGGL((topk_dense_excl_kernel<32, HHFM_TOPK_NV>), dim3((int)blocks), dim3(256), 0,
+                       st, S, B, N, lds, K, base, os, oi, xptr, xrows, item_row_begin);
+  else
+    hipLaunchKernelGGL((topk_dense_excl_kernel<64, HHFM_TOPK_NV>), dim3((int)blocks), dim3(256), 0,
+                       st, S, B, N, lds, K, base, os, oi, xptr, xrows, item_row_begin);
 }
 
 }  // namespace hhfm

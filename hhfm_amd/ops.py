@@ -242,6 +242,16 @@ def _catalog_workspace(dev: torch.device, stream: int, nbytes: int) -> torch.Ten
     return buf
 
 
+def _excl_args(exclude: "ExclusionLists", B: int, dev: torch.device) -> Tuple[int, int, int]:
+    """(excl_ptr, excl_rows, max_excl) of a native *_excl call for B queries."""
+    if exclude.ptr.numel() != B + 1:
+        raise ValueError(f"exclude holds {exclude.ptr.numel() - 1} lists for {B} queries")
+    if _need_cuda(exclude.ptr, exclude.rows) != dev:
+        raise ValueError("exclude must live on the queries' device")
+    return (exclude.ptr.data_ptr(), exclude.rows.data_ptr() if exclude.rows.numel() else 0,
+            int(exclude.max_len))
+
+
 def catalog_topk(qidx: torch.Tensor, E: torch.Tensor, mode: int, K: int,
                  item_row_begin: int, item_count: int, global_item_base: int = 0,
                  w: Optional[torch.Tensor] = None, user_col: int = 0,
@@ -367,11 +377,14 @@ def cars2_score_rows(idx: torch.Tensor, UI: torch.Tensor, prepared: torch.Tensor
 
 def cars2_catalog_topk(q: torch.Tensor, UI: torch.Tensor, prepared: torch.Tensor, Mc: int, K: int,
                        item_row_begin: int, item_count: int, global_item_base: int = 0,
-                       status: Optional[torch.Tensor] = None, plan: int = 0
+                       status: Optional[torch.Tensor] = None, plan: int = 0,
+                       exclude: Optional["ExclusionLists"] = None
                        ) -> Tuple[torch.Tensor, torch.Tensor]:
     """CARS2.topk (CARS2.py:171-187) for queries ``q`` int32 [B, 2] = (user id,
     context id) over UI rows [item_row_begin, +item_count) -> (scores float32
-    [B, K], ids int32 [B, K]); ``plan`` as in :func:`catalog_topk`."""
+    [B, K], ids int32 [B, K]); ``plan`` as in :func:`catalog_topk`.
+    ``exclude``: :class:`ExclusionLists` of UI rows per query
+    (hhfm_cars2_catalog_topk_excl)."""
     _idx(q, "q")
     if q.shape[1] != 2:
         raise ValueError("q must be [rows, 2]: user id, context id")
@@ -386,10 +399,13 @@ def cars2_catalog_topk(q: torch.Tensor, UI: torch.Tensor, prepared: torch.Tensor
     ws = _catalog_workspace(dev, st, nat.catalog_topk_workspace(B, item_count, D, K))
     top_s = torch.empty(B, K, dtype=torch.float32, device=dev)
     top_i = torch.empty(B, K, dtype=torch.int32, device=dev)
-    nat.cars2_catalog_topk(q.data_ptr(), B, UI.data_ptr(), n_ui, D, _dtype_code(UI),
-                           prepared.data_ptr(), Mc, item_row_begin, item_count,
-                           global_item_base, K, top_s.data_ptr(), top_i.data_ptr(),
-                           ws.data_ptr(), ws.numel(), int(plan), _status_ptr(status), st)
+    args = (q.data_ptr(), B, UI.data_ptr(), n_ui, D, _dtype_code(UI), prepared.data_ptr(), Mc,
+            item_row_begin, item_count, global_item_base, K, top_s.data_ptr(), top_i.data_ptr(),
+            ws.data_ptr(), ws.numel(), int(plan), _status_ptr(status), st)
+    if exclude is not None:
+        nat.cars2_catalog_topk_excl(*args, *_excl_args(exclude, B, dev))
+    else:
+        nat.cars2_catalog_topk(*args)
     return top_s, top_i
 
 
@@ -530,16 +546,21 @@ def dfm_catalog_topk(qidx: torch.Tensor, E: torch.Tensor, w: torch.Tensor, Wt, b
                      Wp: torch.Tensor, bp: float, item_col: int, item_row_begin: int,
                      item_count: int, K: int, global_item_base: int = 0,
                      chunk_rows: int = 1 << 20, proj=None, plan: int = 0,
-                     head: Optional[int] = None):
+                     head: Optional[int] = None,
+                     exclude: Optional["ExclusionLists"] = None):
     """DeepFM.topk (DFM.py:219-231) -> (scores [B,K], ids [B,K]); ``proj``,
     ``plan`` and ``head`` as in :func:`dfm_forward` (rows = B x item_count).
     With a head the scores are the pre-sigmoid z whatever DFM_HEAD_SIGMOID says
-    (the sigmoid is monotone: the same id lists)."""
+    (the sigmoid is monotone: the same id lists).  ``exclude``:
+    :class:`ExclusionLists` of table rows per query (hhfm_dfm_catalog_topk_excl;
+    without a head it is the reference default's, fm + deep)."""
     _idx(qidx, "qidx")
     dev = _need_cuda(qidx, E, w, Wp, *Wt, *bias)
     B, F = qidx.shape
     M, k = E.shape
     nat = native()
+    if exclude is not None and head is None:
+        head = dfm_head_word()
     if head is not None:
         md = _dtype_code(Wt[0]) if len(Wt) else 0
         nbytes = nat.dfm_catalog_topk_workspace_ex(B, F, k, M, item_count,
@@ -548,13 +569,16 @@ def dfm_catalog_topk(qidx: torch.Tensor, E: torch.Tensor, w: torch.Tensor, Wt, b
         ws = _workspace(dev, nbytes + _head_ws_extra(head, F, k, dims))
         top_s = torch.empty(B, K, dtype=torch.float32, device=dev)
         top_i = torch.empty(B, K, dtype=torch.int32, device=dev)
-        nat.dfm_catalog_topk_head(qidx.data_ptr(), B, F, item_col, E.data_ptr(), M, k,
-                                  _dtype_code(E), w.data_ptr(), list(dims),
-                                  [t.data_ptr() for t in Wt], [t.data_ptr() for t in bias], md,
-                                  Wp.data_ptr(), float(bp), item_row_begin, item_count,
-                                  global_item_base, K, chunk_rows, top_s.data_ptr(),
-                                  top_i.data_ptr(), DFM_PROJ[proj], int(plan), ws.data_ptr(),
-                                  ws.numel(), _stream(dev), int(head))
+        args = (qidx.data_ptr(), B, F, item_col, E.data_ptr(), M, k, _dtype_code(E),
+                w.data_ptr(), list(dims), [t.data_ptr() for t in Wt],
+                [t.data_ptr() for t in bias], md, Wp.data_ptr(), float(bp), item_row_begin,
+                item_count, global_item_base, K, chunk_rows, top_s.data_ptr(),
+                top_i.data_ptr(), DFM_PROJ[proj], int(plan), ws.data_ptr(), ws.numel(),
+                _stream(dev), int(head))
+        if exclude is not None:
+            nat.dfm_catalog_topk_excl(*args, *_excl_args(exclude, B, dev))
+        else:
+            nat.dfm_catalog_topk_head(*args)
         return top_s, top_i
     md = _dtype_code(Wt[0])
     nbytes = nat.dfm_catalog_topk_workspace_ex(B, F, k, M, item_count, list(dims), md,
@@ -571,10 +595,14 @@ def dfm_catalog_topk(qidx: torch.Tensor, E: torch.Tensor, w: torch.Tensor, Wt, b
     return top_s, top_i
 
 
-def topk_dense(scores: torch.Tensor, K: int, global_item_base: int = 0, plan: int = 0):
+def topk_dense(scores: torch.Tensor, K: int, global_item_base: int = 0, plan: int = 0,
+               exclude: Optional["ExclusionLists"] = None, item_row_begin: int = 0):
     """tf.nn.top_k over a device score matrix [B, N] (K <= 64); ``plan``
     PLAN_ONE_WAVE keeps one wave per query.  The rows may be a column slice of
-    a wider matrix (unit column stride, leading dimension >= N)."""
+    a wider matrix (unit column stride, leading dimension >= N).  ``exclude``:
+    :class:`ExclusionLists` of table rows per matrix row, column i being table
+    row ``item_row_begin + i`` — the top K of the other columns
+    (hhfm_topk_dense_excl; the matrix is not written)."""
     if scores.dtype != torch.float32 or scores.dim() != 2:
         raise TypeError("scores must be float32 [B, N]")
     B, N = scores.shape
@@ -584,9 +612,13 @@ def topk_dense(scores: torch.Tensor, K: int, global_item_base: int = 0, plan: in
         raise ValueError("scores must have unit column stride and a leading dimension >= N")
     top_s = torch.empty(B, K, dtype=torch.float32, device=scores.device)
     top_i = torch.empty(B, K, dtype=torch.int32, device=scores.device)
-    native().topk_dense(scores.data_ptr(), B, N, scores.stride(0) if B > 1 else N, K,
-                        global_item_base,
-                        top_s.data_ptr(), top_i.data_ptr(), int(plan), _stream(scores.device))
+    args = (scores.data_ptr(), B, N, scores.stride(0) if B > 1 else N, K, global_item_base,
+            top_s.data_ptr(), top_i.data_ptr(), int(plan), _stream(scores.device))
+    if exclude is not None:
+        native().topk_dense_excl(*args, int(item_row_begin),
+                                 *_excl_args(exclude, B, scores.device))
+    else:
+        native().topk_dense(*args)
     return top_s, top_i
 
 
@@ -617,9 +649,11 @@ def afm_forward(idx: torch.Tensor, E: torch.Tensor, w: torch.Tensor, w0: float,
 def afm_catalog_topk(qidx: torch.Tensor, E: torch.Tensor, w: torch.Tensor, Wt: torch.Tensor,
                      att_b: torch.Tensor, att_p: torch.Tensor, P: torch.Tensor,
                      item_row_begin: int, item_count: int, K: int, global_item_base: int = 0,
-                     max_cols: int = 1 << 17, plan: int = 0):
+                     max_cols: int = 1 << 17, plan: int = 0,
+                     exclude: Optional["ExclusionLists"] = None):
     """AFM.topk (AFM.py:209-246) -> (scores [B,K], ids [B,K]); ``plan``:
-    PLAN_EXACT_FP32, _PER_FIELD, _GEMM."""
+    PLAN_EXACT_FP32, _PER_FIELD, _GEMM.  ``exclude``: :class:`ExclusionLists`
+    of table rows per query (hhfm_afm_catalog_topk_excl)."""
     _idx(qidx, "qidx")
     dev = _need_cuda(qidx, E, w, Wt, att_b, att_p, P)
     B, F = qidx.shape
@@ -630,22 +664,28 @@ def afm_catalog_topk(qidx: torch.Tensor, E: torch.Tensor, w: torch.Tensor, Wt: t
                                                         int(plan)))
     top_s = torch.empty(B, K, dtype=torch.float32, device=dev)
     top_i = torch.empty(B, K, dtype=torch.int32, device=dev)
-    nat.afm_catalog_topk(qidx.data_ptr(), B, F, E.data_ptr(), M, k, _dtype_code(E), w.data_ptr(),
-                         Wt.data_ptr(), att_b.data_ptr(), att_p.data_ptr(), A, P.data_ptr(),
-                         item_row_begin, item_count, global_item_base, K, max_cols,
-                         top_s.data_ptr(), top_i.data_ptr(), int(plan), ws.data_ptr(), ws.numel(),
-                         _stream(dev))
+    args = (qidx.data_ptr(), B, F, E.data_ptr(), M, k, _dtype_code(E), w.data_ptr(),
+            Wt.data_ptr(), att_b.data_ptr(), att_p.data_ptr(), A, P.data_ptr(), item_row_begin,
+            item_count, global_item_base, K, max_cols, top_s.data_ptr(), top_i.data_ptr(),
+            int(plan), ws.data_ptr(), ws.numel(), _stream(dev))
+    if exclude is not None:
+        nat.afm_catalog_topk_excl(*args, *_excl_args(exclude, B, dev))
+    else:
+        nat.afm_catalog_topk(*args)
     return top_s, top_i
 
 
 def afm_noatt_catalog_topk(qidx: torch.Tensor, E: torch.Tensor, w: Optional[torch.Tensor],
                            w0: float, P: torch.Tensor, item_row_begin: int, item_count: int,
                            K: int, global_item_base: int = 0,
-                           status: Optional[torch.Tensor] = None, plan: int = 0):
+                           status: Optional[torch.Tensor] = None, plan: int = 0,
+                           exclude: Optional["ExclusionLists"] = None):
     """AFM.topk with attention=0 (include/hhfm.h "AFM without attention") ->
     (scores [B,K], ids [B,K]): the score of item i is ``out`` of the query row
     with column 1 replaced by i — this library's definition, the reference's
-    topk raises KeyError here.  ``plan`` as in :func:`catalog_topk`."""
+    topk raises KeyError here.  ``plan`` as in :func:`catalog_topk`.
+    ``exclude``: :class:`ExclusionLists` of table rows per query
+    (hhfm_afm_noatt_catalog_topk_excl)."""
     _idx(qidx, "qidx")
     dev = _need_cuda(qidx, E, w, P)
     B, F = qidx.shape
@@ -659,11 +699,14 @@ def afm_noatt_catalog_topk(qidx: torch.Tensor, E: torch.Tensor, w: Optional[torc
     ws = _catalog_workspace(dev, st, nat.catalog_topk_workspace(B, item_count, k, K))
     top_s = torch.empty(B, K, dtype=torch.float32, device=dev)
     top_i = torch.empty(B, K, dtype=torch.int32, device=dev)
-    nat.afm_noatt_catalog_topk(qidx.data_ptr(), B, F, E.data_ptr(), M, k, _dtype_code(E),
-                               0 if w is None else w.data_ptr(), float(w0), P.data_ptr(),
-                               item_row_begin, item_count, global_item_base, K,
-                               top_s.data_ptr(), top_i.data_ptr(), ws.data_ptr(), ws.numel(),
-                               int(plan), _status_ptr(status), st)
+    args = (qidx.data_ptr(), B, F, E.data_ptr(), M, k, _dtype_code(E),
+            0 if w is None else w.data_ptr(), float(w0), P.data_ptr(), item_row_begin,
+            item_count, global_item_base, K, top_s.data_ptr(), top_i.data_ptr(), ws.data_ptr(),
+            ws.numel(), int(plan), _status_ptr(status), st)
+    if exclude is not None:
+        nat.afm_noatt_catalog_topk_excl(*args, *_excl_args(exclude, B, dev))
+    else:
+        nat.afm_noatt_catalog_topk(*args)
     return top_s, top_i
 
 

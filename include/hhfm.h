@@ -402,9 +402,38 @@ int hhfm_catalog_topk_pool2(const int32_t* qidx, int64_t B, int32_t ncols,
  * that hold an excluded row.  The fused small-catalog kernel and the ring are
  * never taken: HHFM_PLAN_FUSED, _STORE, _NO_RING and _RING_ALT are accepted
  * without effect; _EXACT_FP32, _GEMM, _NO_SEED and _ONE_WAVE keep their meaning.
- * Not built: exclusion forms of the two-way, CARS2, AFM (with or without
- * attention) and DeepFM catalogs, of the ring and of the fused kernel, and
- * lists that run a range short of K.
+ *
+ * The other models' catalogs take the same three arguments after their plain
+ * call's, under the same rules (argument checks before anything is launched,
+ * outputs untouched on an error; scores the plain call's bit for bit; empty
+ * lists give the plain call's output; the plain call's workspace and its
+ * contract: nothing read before the call writes it, the zero prefix left
+ * zero).  The lists are indexed by the call's query number whatever the
+ * call's query chunks (max_cols / chunk_rows):
+ *   hhfm_cars2_catalog_topk_excl      hhfm_cars2_catalog_topk's arguments;
+ *                                     the ids are rows of UI
+ *   hhfm_afm_noatt_catalog_topk_excl  hhfm_afm_noatt_catalog_topk's
+ *     — both on hhfm_catalog_topk_excl's routes behind their own query kernel;
+ *   hhfm_afm_catalog_topk_excl        hhfm_afm_catalog_topk_ex's, on each of
+ *                                     its three scoring routes
+ *   hhfm_dfm_catalog_topk_excl        hhfm_dfm_catalog_topk_head's: the full,
+ *                                     deep-only and FM-only heads
+ *     — both write each query chunk's score block as the plain call does, set
+ *     its listed entries to -FLT_MAX and run the plain dense top-K (the route
+ *     of hhfm_catalog_topk_excl's score matrix; measured faster than the
+ *     select below, DESIGN.md §K2 "Exclusion lists").
+ * hhfm_topk_dense_excl is the dense top-K's own exclusion form on a caller's
+ * matrix, which it reads and never writes: hhfm_topk_dense_ex's
+ * arguments, then item_row_begin (column i is table row item_row_begin + i),
+ * excl_ptr, excl_rows, max_excl.  The top K of each row's non-listed columns
+ * in (score desc, index asc) order, every score the matrix element's own
+ * bits; HHFM_PLAN_ONE_WAVE and the default four waves per query give the same
+ * output bit for bit; max_excl < 0 or K + max_excl > N, and excl_ptr NULL
+ * with B > 0, are HHFM_EINVAL.
+ *
+ * Not built: an exclusion form of the two-way catalog (hhfm_catalog_topk_pool2),
+ * of the ring and of the fused kernel, and lists that run a range short of K
+ * (DESIGN.md §7).
  *
  * hhfm_pf_exclusion_lists builds the lists of `rows` from positive_feedback's
  * device arrays (keys / codes as for hhfm_pf_contains below; in `codes` the
@@ -430,6 +459,47 @@ int hhfm_catalog_topk_excl(const int32_t* qidx, int64_t B, int32_t ncols,
                            size_t ws_bytes, int32_t plan, int32_t pooling,
                            int32_t* status, void* stream, const int64_t* excl_ptr,
                            const int32_t* excl_rows, int64_t max_excl);
+int hhfm_cars2_catalog_topk_excl(const int32_t* q, int64_t B, const void* UI, int64_t n_ui,
+                                 int32_t D, int32_t dtype, const void* prepared, int64_t Mc,
+                                 int32_t item_row_begin, int32_t item_count,
+                                 int32_t global_item_base, int32_t K, float* top_score,
+                                 int32_t* top_idx, void* workspace, size_t ws_bytes,
+                                 int32_t plan, int32_t* status, void* stream,
+                                 const int64_t* excl_ptr, const int32_t* excl_rows,
+                                 int64_t max_excl);
+int hhfm_afm_noatt_catalog_topk_excl(const int32_t* qidx, int64_t B, int32_t F, const void* E,
+                                     int64_t features_M, int32_t k, int32_t dtype,
+                                     const float* w, float w0, const float* P,
+                                     int32_t item_row_begin, int32_t item_count,
+                                     int32_t global_item_base, int32_t K, float* top_score,
+                                     int32_t* top_idx, void* workspace, size_t ws_bytes,
+                                     int32_t plan, int32_t* status, void* stream,
+                                     const int64_t* excl_ptr, const int32_t* excl_rows,
+                                     int64_t max_excl);
+int hhfm_afm_catalog_topk_excl(const int32_t* qidx, int64_t B, int32_t F, const void* E,
+                               int64_t features_M, int32_t k, int32_t dtype, const float* w,
+                               const float* Wt, const float* att_b, const float* att_p,
+                               int32_t A, const float* P, int32_t item_row_begin,
+                               int32_t item_count, int32_t global_item_base, int32_t K,
+                               int64_t max_cols, float* top_score, int32_t* top_idx,
+                               int32_t plan, void* workspace, size_t ws_bytes, void* stream,
+                               const int64_t* excl_ptr, const int32_t* excl_rows,
+                               int64_t max_excl);
+int hhfm_dfm_catalog_topk_excl(const int32_t* qidx, int64_t B, int32_t F, int32_t item_col,
+                               const void* E, int64_t features_M, int32_t k, int32_t dtype,
+                               const float* w, int32_t nlayers, const int32_t* layer_dims,
+                               const void* const* Wt, const float* const* bias,
+                               int32_t mlp_dtype, const float* Wp, float bp,
+                               int32_t item_row_begin, int32_t item_count,
+                               int32_t global_item_base, int32_t K, int64_t chunk_rows,
+                               float* top_score, int32_t* top_idx, int32_t proj_mode,
+                               int32_t plan, void* workspace, size_t ws_bytes, void* stream,
+                               int32_t head, const int64_t* excl_ptr, const int32_t* excl_rows,
+                               int64_t max_excl);
+int hhfm_topk_dense_excl(const float* scores, int64_t B, int32_t N, int64_t ld, int32_t K,
+                         int32_t global_item_base, float* top_score, int32_t* top_idx,
+                         int32_t plan, void* stream, int32_t item_row_begin,
+                         const int64_t* excl_ptr, const int32_t* excl_rows, int64_t max_excl);
 int hhfm_pf_exclusion_lists_workspace(int64_t B, size_t* ws_bytes);
 int hhfm_pf_exclusion_lists(const int32_t* keys, int64_t nkeys, int32_t key_cols,
                             const int64_t* codes, int64_t ncodes, const int32_t* rows,

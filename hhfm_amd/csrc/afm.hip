@@ -20,6 +20,7 @@
 #include <atomic>
 
 #include "gemm_mfma.h"
+#include "topk_wide.h"
 
 namespace hhfm {
 
@@ -1423,7 +1424,7 @@ static int afm_catalog_impl(const int32_t* qidx, int64_t B, int32_t F, const voi
   if (item_count < 1 || item_row_begin < 0 || (int64_t)item_row_begin + item_count > features_M)
     return HHFM_EINVAL;
   if (K < 1 || K > item_count) return HHFM_EINVAL;
-  if (K > 64) return HHFM_EUNSUPPORTED;
+  if (K > HHFM_TOPK_MAX_K) return HHFM_EUNSUPPORTED;
   if (excl && !excl_args_ok(*excl, B, item_count, K)) return HHFM_EINVAL;
   if (!afm_cat_fused_ok(F, k, A, plan) && (k % 4 || A % 16))
     return HHFM_EUNSUPPORTED;
@@ -1560,7 +1561,10 @@ static int afm_catalog_impl(const int32_t* qidx, int64_t B, int32_t F, const voi
     if (excl)   // the lists are indexed by the call's query number; sc is this chunk's alone
       launch_excl_mask_scores(ExclLists{excl->ptr + b0, excl->rows, 0}, nq, item_row_begin,
                               item_count, sc, item_count, st);
-    if (K <= 32)
+    if (K > kTopkNarrowMaxK)   // include/hhfm.h "Wide K"
+      launch_topk_wide_dense(sc, nq, item_count, (int64_t)item_count, K, global_item_base,
+                             top_score + b0 * K, top_idx + b0 * K, st);
+    else if (K <= 32)
       hipLaunchKernelGGL((topk_dense_kernel<32, 32>), dim3((unsigned)tblocks), dim3(256), 0, st, sc, nq,
                          item_count, (int64_t)item_count, K, global_item_base,
                          top_score + b0 * K, top_idx + b0 * K, nullptr);

@@ -23,6 +23,7 @@
 // Order everywhere: score descending, item index ascending (tf.nn.top_k).
 #include "cars2.h"
 #include "gemm_mfma.h"
+#include "topk_wide.h"
 #include "hhfm_feature.h"
 
 #include <algorithm>
@@ -1532,9 +1533,151 @@ static void launch_merge(const float* in_s, const int32_t* in_i, int R, int64_t 
                        in_s, in_i, R, B, K, stride_r, stride_b, os, oi);
 }
 
+// ---------------------------------------------------------------------------
+// wide K (include/hhfm.h "Wide K"): score blocks + topk_wide.hip
+// ---------------------------------------------------------------------------
+// Items per score block of a catalog beyond the dense limit: the dense limit,
+// fewer (a multiple of the item tile) when B of them would pass the dense
+// route's 64 M cells.  Below 1,024 items a block would be mostly launch
+// overhead, so that is the floor: past 65,536 queries the block matrix grows
+// with B again (4 KiB per query).
+static int32_t wide_block_items(int64_t B) {
+  constexpr int64_t kMax = 16384, kCells = (int64_t)64 << 20;
+  if (B * kMax <= kCells) return (int32_t)kMax;
+  const int64_t nb = (kCells / B) & ~int64_t(kTile - 1);
+  return (int32_t)(nb < 1024 ? 1024 : nb);
+}
+
+// H, cst and the threshold words where every narrow plan has them; behind them
+// the score block [B][ldsc] and, when the catalog takes more than one block,
+// three sets of [B][K] lists (the running list, the block's, the merge's output)
+struct WidePlan {
+  int32_t nb;        // items per block (the whole catalog when it is dense)
+  int64_t ldsc;
+  bool lists;
+  size_t off_sc, off_ls, off_li, total;
+};
+
+static WidePlan make_wide_plan(int64_t B, int32_t N, int32_t k, int32_t K) {
+  WidePlan wp{};
+  // (off_ps: the first byte behind H / cst / thr — a function of B and k alone)
+  const Plan p = make_plan(B, N < 16384 ? N : 16384, k, kTopkNarrowMaxK, HHFM_PLAN_DEFAULT, false);
+  const int32_t blk = dense_catalog(B, N) ? N : wide_block_items(B);
+  wp.nb = N < blk ? N : blk;
+  wp.lists = wp.nb < N;
+  wp.ldsc = (wp.nb + 3) & ~3;
+  size_t off = p.off_ps;
+  wp.off_sc = off;
+  off += align256((size_t)B * wp.ldsc * sizeof(float));
+  wp.off_ls = off;
+  if (wp.lists) off += align256((size_t)3 * B * K * sizeof(float));
+  wp.off_li = off;
+  if (wp.lists) off += align256((size_t)3 * B * K * sizeof(int32_t));
+  wp.total = off;
+  return wp;
+}
+
+// What a wide call needs and what hhfm_catalog_topk_wide_workspace answers:
+// the wide layout, and never less than the K = 64 narrow query of the same
+// sizes.  Beyond the dense limit the answer may not depend on item_count, so
+// the narrow plan is taken at N = 2^30 there, which bounds it for every N:
+// of make_plan's regions only two depend on N once the catalog is not dense.
+//   - the partial lists, B * nsplit * K entries: every split count is
+//     ceil(ntiles / ceil(ntiles / s)) <= s with s = min(c, ntiles / 16) and c
+//     the workgroup target over the query groups (<= 512, a function of B
+//     alone); at 2^25 tiles s = c and c * c <= ntiles, so the count is c
+//     itself, the largest any N reaches;
+//   - the seed, min(budget / Bpad, kSeedMax, N / 16) items rounded down to 32:
+//     non-decreasing in N and at its cap once N / 16 passes kSeedMax.
+// (tests/test_topk_wide_ref.py sweeps N against the narrow query.)
+static size_t wide_ws_bytes(int64_t B, int32_t N, int32_t k, int32_t K) {
+  const int32_t nn = N > 16384 ? (1 << 30) : N;
+  const size_t a = make_plan(B, nn, k, kTopkNarrowMaxK, HHFM_PLAN_DEFAULT, false).total;
+  const size_t b = make_plan(B, nn, k, kTopkNarrowMaxK, HHFM_PLAN_DEFAULT, true).total;
+  const size_t c = make_wide_plan(B, N, k, K).total;
+  return std::max(a, std::max(b, c));
+}
+
+// The route behind the query kernel (H, cst written): block after block of at
+// most wp.nb items scored into the block matrix by the narrow call's own score
+// kernels — dispatch_store, or the GEMM where the narrow call takes it — masked
+// at listed columns, selected by topk_wide_dense with the block's id base, and
+// merged into the running list.  The lists ping-pong between slots 0 and 2
+// around the block's list in slot 1, so no merge writes what it reads.
+static int catalog_wide_route(const Plan& p, const WidePlan& wp, char* ws, int64_t B, const char* Eb,
+                              bool bf16, int KT, int32_t k, int32_t mode, const float* w,
+                              const float* H, const float* cst, int32_t* gthr,
+                              int32_t item_row_begin, int32_t N, int32_t gbase, int32_t K,
+                              float* top_score, int32_t* top_idx, int32_t plan,
+                              const ExclLists* excl, hipStream_t st) {
+  float* sc = reinterpret_cast<float*>(ws + wp.off_sc);
+  float* ls = reinterpret_cast<float*>(ws + wp.off_ls);
+  int32_t* li = reinterpret_cast<int32_t*>(ws + wp.off_li);
+  const bool fmm = mode == HHFM_MODE_FM;
+  const float* wv = (fmm && w) ? w : nullptr;
+  const bool gemm_asked = !wp.lists && p.dense && (plan & HHFM_PLAN_GEMM);
+  const int64_t BK = B * (int64_t)K;
+  int run = 0;   // slot of the running list
+  for (int32_t i0 = 0; i0 < N; i0 += wp.nb) {
+    const int32_t n = N - i0 < wp.nb ? N - i0 : wp.nb;
+    const bool last = i0 + n >= N;
+    const int64_t irb = (int64_t)item_row_begin + i0;
+    bool ok = false;
+    if (!gemm_asked) {
+      if (bf16) ok = fmm ? dispatch_store<true, true>(KT, B, p.nqb, n, H, cst, Eb, irb, wv, sc, wp.ldsc, gthr, plan, st)
+                         : dispatch_store<true, false>(KT, B, p.nqb, n, H, cst, Eb, irb, wv, sc, wp.ldsc, gthr, plan, st);
+      else ok = fmm ? dispatch_store<false, true>(KT, B, p.nqb, n, H, cst, Eb, irb, wv, sc, wp.ldsc, gthr, plan, st)
+                    : dispatch_store<false, false>(KT, B, p.nqb, n, H, cst, Eb, irb, wv, sc, wp.ldsc, gthr, plan, st);
+    }
+    if (!ok) {
+      if (wp.lists || !p.dense) return HHFM_EUNSUPPORTED;   // (the narrow streaming route has no GEMM)
+      GemmArgs g{};
+      g.M = B;
+      g.N = n;
+      g.K = k;
+      g.A = H;
+      g.lda = k;
+      g.Bt = Eb + irb * k * (bf16 ? 2 : 4);
+      g.ldb = k;
+      g.b_src_bf16 = bf16;
+      g.bias = (fmm && w) ? w + irb : nullptr;
+      g.rowbias = fmm ? cst : nullptr;
+      g.C = sc;
+      g.ldc = wp.ldsc;
+      launch_gemm(g, false, 0, st);
+    }
+    if (excl) launch_excl_mask(*excl, B, irb, n, 0, sc, wp.ldsc, st);
+    const bool direct = i0 == 0 && last;
+    float* ds = direct ? top_score : ls + (i0 == 0 ? 0 : BK);
+    int32_t* di = direct ? top_idx : li + (i0 == 0 ? 0 : BK);
+    launch_topk_wide_dense(sc, B, n, wp.ldsc, K, gbase + i0, ds, di, st);
+    if (i0 > 0) {
+      const int64_t stride_r = (int64_t)(1 - run) * BK;   // slot run, then slot 1
+      launch_topk_wide_merge(ls + run * BK, li + run * BK, 2, B, K, stride_r, K,
+                             last ? top_score : ls + (2 - run) * BK,
+                             last ? top_idx : li + (2 - run) * BK, st);
+      run = 2 - run;
+    }
+  }
+  return (int)hipGetLastError();
+}
+
 }  // namespace hhfm
 
 using namespace hhfm;
+
+extern "C" int hhfm_catalog_topk_wide_workspace(int64_t B, int32_t item_count, int32_t k,
+                                                int32_t K, size_t* ws_bytes) {
+  if (!ws_bytes || B < 0 || item_count < 1 || k < 1 || K < 1 || K > HHFM_TOPK_MAX_K)
+    return HHFM_EINVAL;
+  if (B == 0) {   // a call without queries returns before it looks at its workspace
+    *ws_bytes = 0;
+    return HHFM_OK;
+  }
+  if (K <= kTopkNarrowMaxK) return hhfm_catalog_topk_workspace(B, item_count, k, K, ws_bytes);
+  *ws_bytes = wide_ws_bytes(B, item_count, k, K);
+  return HHFM_OK;
+}
 
 extern "C" int hhfm_catalog_topk_workspace(int64_t B, int32_t item_count,
                                            int32_t k, int32_t K,
@@ -1596,7 +1739,8 @@ static int catalog_topk_impl(
       (int64_t)item_row_begin + item_count > features_M)
     return HHFM_EINVAL;
   if (K < 1 || K > item_count) return HHFM_EINVAL;
-  if (K > 64) return HHFM_EUNSUPPORTED;
+  if (K > HHFM_TOPK_MAX_K) return HHFM_EUNSUPPORTED;
+  const bool wide = K > kTopkNarrowMaxK;   // include/hhfm.h "Wide K"
   // exclusion lists: K admissible items must remain whatever the lists hold
   if (excl && !excl_args_ok(*excl, B, item_count, K)) return HHFM_EINVAL;
   const bool bf16 = dtype == HHFM_BF16;
@@ -1608,8 +1752,10 @@ static int catalog_topk_impl(
   if (!qidx || !E || !top_score || !top_idx) return HHFM_EINVAL;
   if ((reinterpret_cast<uintptr_t>(E) & 15) != 0) return HHFM_EUNSUPPORTED;
 
-  const Plan p = make_plan(B, item_count, k, K, plan, bf16);
-  if (!workspace || ws_bytes < p.total) return HHFM_EWORKSPACE;
+  // (wide: H, cst and the threshold words lie where every narrow plan has them)
+  const Plan p = make_plan(B, item_count, k, wide ? kTopkNarrowMaxK : K, plan, bf16);
+  if (!workspace || ws_bytes < (wide ? wide_ws_bytes(B, item_count, k, K) : p.total))
+    return HHFM_EWORKSPACE;
   char* ws = reinterpret_cast<char*>(workspace);
   float* H = reinterpret_cast<float*>(ws + p.off_H);
   float* cst = reinterpret_cast<float*>(ws + p.off_cst);
@@ -1676,6 +1822,11 @@ static int catalog_topk_impl(
     else
       queries(SumFeature{});
   }
+
+  if (wide)   // never the fused kernel (K <= 32 above), the ring or the seed
+    return catalog_wide_route(p, make_wide_plan(B, item_count, k, K), ws, B, Eb, bf16, KT, k, mode,
+                              w, H, cst, gthr, item_row_begin, item_count, global_item_base, K,
+                              top_score, top_idx, plan, excl, st);
 
   if (p.dense) {
     float* sc = reinterpret_cast<float*>(ws + p.off_sc);
@@ -1995,9 +2146,15 @@ extern "C" int hhfm_topk_merge(const float* in_score, const int32_t* in_idx,
                                int32_t R, int64_t B, int32_t K, float* out_score,
                                int32_t* out_idx, void* stream) {
   if (R < 1 || B < 0 || K < 1) return HHFM_EINVAL;
-  if (K > 64) return HHFM_EUNSUPPORTED;
+  if (K > HHFM_TOPK_MAX_K) return HHFM_EUNSUPPORTED;
   if (B == 0) return HHFM_OK;
   if (!in_score || !in_idx || !out_score || !out_idx) return HHFM_EINVAL;
+  if (K > kTopkNarrowMaxK) {   // include/hhfm.h "Wide K"
+    if ((int64_t)R * K > 0x7fffffff) return HHFM_EUNSUPPORTED;
+    launch_topk_wide_merge(in_score, in_idx, R, B, K, /*stride_r=*/B * K, /*stride_b=*/K,
+                           out_score, out_idx, reinterpret_cast<hipStream_t>(stream));
+    return (int)hipGetLastError();
+  }
   launch_merge(in_score, in_idx, R, B, K, /*stride_r=*/B * K, /*stride_b=*/K,
                out_score, out_idx, reinterpret_cast<hipStream_t>(stream));
   return (int)hipGetLastError();

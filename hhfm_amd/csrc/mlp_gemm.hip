@@ -23,6 +23,7 @@
 #include <cstdlib>
 
 #include "gemm_mfma.h"
+#include "topk_wide.h"
 
 namespace hhfm {
 
@@ -547,7 +548,7 @@ static int dfm_catalog_run(const int32_t* qidx, int64_t B, int32_t F, int32_t it
       (int64_t)item_row_begin + item_count > features_M || chunk_rows < 1)
     return HHFM_EINVAL;
   if (K < 1 || K > item_count) return HHFM_EINVAL;
-  if (K > 64) return HHFM_EUNSUPPORTED;
+  if (K > HHFM_TOPK_MAX_K) return HHFM_EUNSUPPORTED;
   if (excl && !excl_args_ok(*excl, B, item_count, K)) return HHFM_EINVAL;
   if (B == 0) return HHFM_OK;
   if (!qidx || !E || !w || !Wt || !bias || !Wp || !top_score || !top_idx) return HHFM_EINVAL;
@@ -601,8 +602,12 @@ static int dfm_catalog_run(const int32_t* qidx, int64_t B, int32_t F, int32_t it
     if (excl)   // the lists are indexed by the call's query number; sc is this chunk's alone
       launch_excl_mask_scores(ExclLists{excl->ptr + b0, excl->rows, 0}, nb, item_row_begin,
                               item_count, sc, item_count, st);
-    launch_topk_dense(sc, nb, item_count, item_count, K, global_item_base, top_score + b0 * K,
-                      top_idx + b0 * K, st, (plan & HHFM_PLAN_ONE_WAVE) != 0);
+    if (K > kTopkNarrowMaxK)   // include/hhfm.h "Wide K"
+      launch_topk_wide_dense(sc, nb, item_count, item_count, K, global_item_base,
+                             top_score + b0 * K, top_idx + b0 * K, st);
+    else
+      launch_topk_dense(sc, nb, item_count, item_count, K, global_item_base, top_score + b0 * K,
+                        top_idx + b0 * K, st, (plan & HHFM_PLAN_ONE_WAVE) != 0);
   }
   return (int)hipGetLastError();
 }
@@ -656,7 +661,7 @@ static int dfm_catalog_fm(const int32_t* qidx, int64_t B, int32_t F, int32_t ite
       (int64_t)item_row_begin + item_count > features_M || chunk_rows < 1)
     return HHFM_EINVAL;
   if (K < 1 || K > item_count) return HHFM_EINVAL;
-  if (K > 64) return HHFM_EUNSUPPORTED;
+  if (K > HHFM_TOPK_MAX_K) return HHFM_EUNSUPPORTED;
   if (excl && !excl_args_ok(*excl, B, item_count, K)) return HHFM_EINVAL;
   if (B == 0) return HHFM_OK;
   if (!qidx || !E || !w || !Wp || !top_score || !top_idx) return HHFM_EINVAL;
@@ -680,8 +685,12 @@ static int dfm_catalog_fm(const int32_t* qidx, int64_t B, int32_t F, int32_t ite
     if (excl)   // the lists are indexed by the call's query number; sc is this chunk's alone
       launch_excl_mask_scores(ExclLists{excl->ptr + b0, excl->rows, 0}, nb, item_row_begin,
                               item_count, sc, item_count, st);
-    launch_topk_dense(sc, nb, item_count, item_count, K, global_item_base, top_score + b0 * K,
-                      top_idx + b0 * K, st, (plan & HHFM_PLAN_ONE_WAVE) != 0);
+    if (K > kTopkNarrowMaxK)   // include/hhfm.h "Wide K"
+      launch_topk_wide_dense(sc, nb, item_count, item_count, K, global_item_base,
+                             top_score + b0 * K, top_idx + b0 * K, st);
+    else
+      launch_topk_dense(sc, nb, item_count, item_count, K, global_item_base, top_score + b0 * K,
+                        top_idx + b0 * K, st, (plan & HHFM_PLAN_ONE_WAVE) != 0);
   }
   return (int)hipGetLastError();
 }
@@ -733,9 +742,14 @@ extern "C" int hhfm_topk_dense(const float* scores, int64_t B, int32_t N, int64_
                                int32_t global_item_base, float* top_score, int32_t* top_idx,
                                void* stream) {
   if (B < 0 || N < 1 || ld < N || K < 1 || K > N) return HHFM_EINVAL;
-  if (K > 64) return HHFM_EUNSUPPORTED;
+  if (K > HHFM_TOPK_MAX_K) return HHFM_EUNSUPPORTED;
   if (B == 0) return HHFM_OK;
   if (!scores || !top_score || !top_idx) return HHFM_EINVAL;
+  if (K > kTopkNarrowMaxK) {   // include/hhfm.h "Wide K"
+    launch_topk_wide_dense(scores, B, N, ld, K, global_item_base, top_score, top_idx,
+                           reinterpret_cast<hipStream_t>(stream));
+    return (int)hipGetLastError();
+  }
   launch_topk_dense(scores, B, N, ld, K, global_item_base, top_score, top_idx,
                     reinterpret_cast<hipStream_t>(stream));
   return (int)hipGetLastError();
@@ -745,9 +759,14 @@ extern "C" int hhfm_topk_dense_ex(const float* scores, int64_t B, int32_t N, int
                                   int32_t K, int32_t global_item_base, float* top_score,
                                   int32_t* top_idx, int32_t plan, void* stream) {
   if (!plan_ok(plan) || B < 0 || N < 1 || ld < N || K < 1 || K > N) return HHFM_EINVAL;
-  if (K > 64) return HHFM_EUNSUPPORTED;
+  if (K > HHFM_TOPK_MAX_K) return HHFM_EUNSUPPORTED;
   if (B == 0) return HHFM_OK;
   if (!scores || !top_score || !top_idx) return HHFM_EINVAL;
+  if (K > kTopkNarrowMaxK) {   // include/hhfm.h "Wide K": the plan chooses nothing
+    launch_topk_wide_dense(scores, B, N, ld, K, global_item_base, top_score, top_idx,
+                           reinterpret_cast<hipStream_t>(stream));
+    return (int)hipGetLastError();
+  }
   launch_topk_dense(scores, B, N, ld, K, global_item_base, top_score, top_idx,
                     reinterpret_cast<hipStream_t>(stream), (plan & HHFM_PLAN_ONE_WAVE) != 0);
   return (int)hipGetLastError();
@@ -762,10 +781,16 @@ extern "C" int hhfm_topk_dense_excl(const float* scores, int64_t B, int32_t N, i
                                     int32_t item_row_begin, const int64_t* excl_ptr,
                                     const int32_t* excl_rows, int64_t max_excl) {
   if (!plan_ok(plan) || B < 0 || N < 1 || ld < N || K < 1 || K > N) return HHFM_EINVAL;
-  if (K > 64) return HHFM_EUNSUPPORTED;
+  if (K > HHFM_TOPK_MAX_K) return HHFM_EUNSUPPORTED;
   if (!excl_args_ok(ExclLists{excl_ptr, excl_rows, max_excl}, B, N, K)) return HHFM_EINVAL;
   if (B == 0) return HHFM_OK;
   if (!scores || !top_score || !top_idx) return HHFM_EINVAL;
+  if (K > kTopkNarrowMaxK) {   // include/hhfm.h "Wide K": the matrix stays read-only
+    launch_topk_wide_dense_excl(scores, B, N, ld, K, global_item_base, top_score, top_idx,
+                                reinterpret_cast<hipStream_t>(stream), excl_ptr, excl_rows,
+                                item_row_begin);
+    return (int)hipGetLastError();
+  }
   launch_topk_dense_excl(scores, B, N, ld, K, global_item_base, top_score, top_idx,
                          reinterpret_cast<hipStream_t>(stream),
                          (plan & HHFM_PLAN_ONE_WAVE) != 0, excl_ptr, excl_rows, item_row_begin);

@@ -46,6 +46,7 @@ PYBIND11_MODULE(_hhfm, m) {
   m.doc() = "pybind11 binding of libhhfm (MI355X FM-family scoring kernels)";
   m.attr("ABI_VERSION") = HHFM_ABI_VERSION;
   m.attr("CATALOG_WS_ZERO") = (int64_t)HHFM_CATALOG_WS_ZERO;
+  m.attr("TOPK_MAX_K") = (int)HHFM_TOPK_MAX_K;
   m.attr("F32") = (int)HHFM_F32;
   m.attr("BF16") = (int)HHFM_BF16;
   m.attr("MODE_FM") = (int)HHFM_MODE_FM;
@@ -367,6 +368,14 @@ PYBIND11_MODULE(_hhfm, m) {
           size_t ws = 0;
           check(hhfm_catalog_topk_workspace(B, item_count, k, K, &ws),
                 "hhfm_catalog_topk_workspace");
+          return ws;
+        });
+
+  m.def("catalog_topk_wide_workspace",
+        [](int64_t B, int item_count, int k, int K) {
+          size_t ws = 0;
+          check(hhfm_catalog_topk_wide_workspace(B, item_count, k, K, &ws),
+                "hhfm_catalog_topk_wide_workspace");
           return ws;
         });
 

@@ -242,6 +242,24 @@ def _catalog_workspace(dev: torch.device, stream: int, nbytes: int) -> torch.Ten
     return buf
 
 
+TOPK_MAX_K = 1024       # HHFM_TOPK_MAX_K
+_TOPK_NARROW_MAX_K = 64  # above it: the wide select (include/hhfm.h "Wide K")
+
+
+def _check_topk_k(K: int) -> int:
+    K = int(K)
+    if K < 1 or K > TOPK_MAX_K:
+        raise ValueError(f"K = {K}: top-K lists hold 1 to {TOPK_MAX_K} entries (TOPK_MAX_K)")
+    return K
+
+
+def _catalog_ws_bytes(nat, B: int, item_count: int, k: int, K: int) -> int:
+    """The shared catalog workspace's size: the wide query above 64 entries."""
+    if _check_topk_k(K) > _TOPK_NARROW_MAX_K:
+        return nat.catalog_topk_wide_workspace(B, item_count, k, K)
+    return nat.catalog_topk_workspace(B, item_count, k, K)
+
+
 def _excl_args(exclude: "ExclusionLists", B: int, dev: torch.device) -> Tuple[int, int, int]:
     """(excl_ptr, excl_rows, max_excl) of a native *_excl call for B queries."""
     if exclude.ptr.numel() != B + 1:
@@ -275,7 +293,7 @@ def catalog_topk(qidx: torch.Tensor, E: torch.Tensor, mode: int, K: int,
     word2 = pooling_word(pooling2)
     nat = native()
     st = _stream(dev)
-    ws = _catalog_workspace(dev, st, nat.catalog_topk_workspace(B, item_count, k, K))
+    ws = _catalog_workspace(dev, st, _catalog_ws_bytes(nat, B, item_count, k, K))
     top_s = torch.empty(B, K, dtype=torch.float32, device=dev)
     top_i = torch.empty(B, K, dtype=torch.int32, device=dev)
     if exclude is not None:
@@ -396,7 +414,7 @@ def cars2_catalog_topk(q: torch.Tensor, UI: torch.Tensor, prepared: torch.Tensor
         raise ValueError("prepared must be cars2_prepare's float32 tensor for this Mc and D")
     nat = native()
     st = _stream(dev)
-    ws = _catalog_workspace(dev, st, nat.catalog_topk_workspace(B, item_count, D, K))
+    ws = _catalog_workspace(dev, st, _catalog_ws_bytes(nat, B, item_count, D, K))
     top_s = torch.empty(B, K, dtype=torch.float32, device=dev)
     top_i = torch.empty(B, K, dtype=torch.int32, device=dev)
     args = (q.data_ptr(), B, UI.data_ptr(), n_ui, D, _dtype_code(UI), prepared.data_ptr(), Mc,
@@ -411,8 +429,9 @@ def cars2_catalog_topk(q: torch.Tensor, UI: torch.Tensor, prepared: torch.Tensor
 
 def topk_merge(scores: torch.Tensor, ids: torch.Tensor
                ) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Merge R sorted [B,K] lists (stacked [R,B,K], rank-major) into [B,K].
-    Device tensors use the HIP kernel; host tensors the C++ host merge."""
+    """Merge R sorted [B,K] lists (stacked [R,B,K], rank-major) into [B,K],
+    K <= TOPK_MAX_K.  Device tensors use the HIP kernels (the wide merge above
+    64 entries); host tensors the C++ host merge."""
     if scores.dim() != 3 or scores.shape != ids.shape:
         raise ValueError("expected scores/ids of shape [R, B, K]")
     if scores.dtype != torch.float32 or ids.dtype != torch.int32:
@@ -425,6 +444,7 @@ def topk_merge(scores: torch.Tensor, ids: torch.Tensor
     nat = native()
     if scores.is_cuda:
         _need_cuda(scores, ids)
+        _check_topk_k(K)
         nat.topk_merge(scores.data_ptr(), ids.data_ptr(), R, B, K, out_s.data_ptr(),
                        out_i.data_ptr(), _stream(scores.device))
     else:
@@ -558,6 +578,7 @@ def dfm_catalog_topk(qidx: torch.Tensor, E: torch.Tensor, w: torch.Tensor, Wt, b
     dev = _need_cuda(qidx, E, w, Wp, *Wt, *bias)
     B, F = qidx.shape
     M, k = E.shape
+    K = _check_topk_k(K)
     nat = native()
     if exclude is not None and head is None:
         head = dfm_head_word()
@@ -597,7 +618,8 @@ def dfm_catalog_topk(qidx: torch.Tensor, E: torch.Tensor, w: torch.Tensor, Wt, b
 
 def topk_dense(scores: torch.Tensor, K: int, global_item_base: int = 0, plan: int = 0,
                exclude: Optional["ExclusionLists"] = None, item_row_begin: int = 0):
-    """tf.nn.top_k over a device score matrix [B, N] (K <= 64); ``plan``
+    """tf.nn.top_k over a device score matrix [B, N] (K <= TOPK_MAX_K; above
+    64 entries the wide select, which no plan bit changes); ``plan``
     PLAN_ONE_WAVE keeps one wave per query.  The rows may be a column slice of
     a wider matrix (unit column stride, leading dimension >= N).  ``exclude``:
     :class:`ExclusionLists` of table rows per matrix row, column i being table
@@ -606,6 +628,7 @@ def topk_dense(scores: torch.Tensor, K: int, global_item_base: int = 0, plan: in
     if scores.dtype != torch.float32 or scores.dim() != 2:
         raise TypeError("scores must be float32 [B, N]")
     B, N = scores.shape
+    K = _check_topk_k(K)
     if not scores.is_cuda:
         raise ValueError("hhfm_amd kernels take device (cuda/HIP) tensors")
     if N > 1 and scores.stride(1) != 1 or B > 1 and scores.stride(0) < N:
@@ -659,6 +682,7 @@ def afm_catalog_topk(qidx: torch.Tensor, E: torch.Tensor, w: torch.Tensor, Wt: t
     B, F = qidx.shape
     M, k = E.shape
     A = Wt.shape[0]
+    K = _check_topk_k(K)
     nat = native()
     ws = _workspace(dev, nat.afm_catalog_topk_workspace(B, F, k, A, item_count, max_cols,
                                                         int(plan)))
@@ -696,7 +720,7 @@ def afm_noatt_catalog_topk(qidx: torch.Tensor, E: torch.Tensor, w: Optional[torc
         raise ValueError("w must be float32 with features_M entries")
     nat = native()
     st = _stream(dev)
-    ws = _catalog_workspace(dev, st, nat.catalog_topk_workspace(B, item_count, k, K))
+    ws = _catalog_workspace(dev, st, _catalog_ws_bytes(nat, B, item_count, k, K))
     top_s = torch.empty(B, K, dtype=torch.float32, device=dev)
     top_i = torch.empty(B, K, dtype=torch.int32, device=dev)
     args = (qidx.data_ptr(), B, F, E.data_ptr(), M, k, _dtype_code(E),

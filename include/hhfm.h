@@ -283,7 +283,8 @@ int hhfm_hybrid_score_rows_pool2(const int32_t* idx, int64_t B, int32_t ncols,
  *   catalog: items are rows [item_row_begin, item_row_begin+item_count) of E.
  *   output:  top_score/top_idx [B][K], sorted by (score desc, index asc) —
  *            tf.nn.top_k order; top_idx = global_item_base + offset in range.
- *   K must be in [1, 64] and <= item_count.
+ *   K must be in [1, HHFM_TOPK_MAX_K] and <= item_count ("Wide K" below for
+ *            K > 64).
  *   arithmetic: the h·item products run on bf16 MFMA with every fp32
  *            operand split exactly into three bf16 pieces (products of
  *            order >= 2^-16 kept, fp32 accumulation: ~1e-7 relative to a
@@ -317,6 +318,48 @@ int hhfm_hybrid_score_rows_pool2(const int32_t* idx, int64_t B, int32_t ncols,
  * ---------------------------------------------------------------------- */
 int hhfm_catalog_topk_workspace(int64_t B, int32_t item_count, int32_t k,
                                 int32_t K, size_t* ws_bytes);
+
+/* ------------------------------------------------------------------------
+ * Wide K: 65 <= K <= HHFM_TOPK_MAX_K ("narrow" is K <= 64) — ABI v6, additions
+ * only.  Every catalog entry point of this header (hhfm_catalog_topk and its
+ * _ex, _pool, _pool2 and _excl forms, the CARS2 and AFM-without-attention
+ * forms, hhfm_afm_catalog_topk*, hhfm_dfm_catalog_topk*), hhfm_topk_dense,
+ * _dense_ex, _dense_excl and hhfm_topk_merge take a wide K with the signature
+ * and the meaning of the narrow call:
+ *   order:   score descending, index ascending on equal scores; a wide list is
+ *            that order carried further, so for K' < K the top-K' list is the
+ *            first K' entries of the top-K list, scores bit for bit (+0 and
+ *            -0 are equal scores ordered by index, as in the narrow kernels,
+ *            and each comes out with its own sign bit).
+ *   scores:  those of the narrow call under the same HHFM_PLAN_EXACT_FP32 /
+ *            HHFM_PLAN_GEMM bits (the same products in the same k order).  Plan
+ *            bits that choose among narrow selection kernels (_NO_SEED,
+ *            _NO_RING, _RING_ALT, _FUSED, _STORE, _ONE_WAVE) are accepted and
+ *            have no effect.
+ *   unchanged: the score range, the id status word, global_item_base, the
+ *            exclusion lists and their K + max_excl <= item_count rule.
+ *   errors:  K > item_count is HHFM_EINVAL (checked first),
+ *            K > HHFM_TOPK_MAX_K HHFM_EUNSUPPORTED.
+ * Route (hhfm_catalog_topk family): the score matrix of a small catalog, or
+ * of one block of at most 16,384 items after another of a large one, is
+ * written by the narrow call's own score kernels, masked at listed columns,
+ * and selected by one workgroup per query that keeps its list in LDS; the
+ * blocks' lists are merged into a running list.
+ * Workspace of that family: hhfm_catalog_topk_wide_workspace, a host-only
+ * query valid for 1 <= K <= HHFM_TOPK_MAX_K (hhfm_catalog_topk_workspace keeps
+ * refusing K > 64).  For K <= 64 it is the narrow query.  For K > 64 it covers
+ * one score block plus the running lists and does not grow with item_count
+ * beyond 16,384.  A wide call on a smaller buffer returns HHFM_EWORKSPACE
+ * before anything is launched.  The rules above hold unchanged: the first
+ * HHFM_CATALOG_WS_ZERO bytes zero before the first call and left zero by every
+ * call (the wide route never writes there), the rest may hold anything, one
+ * buffer serves any mix of narrow and wide calls it is large enough for.  The
+ * AFM and DeepFM catalogs select from the score block they already own: their
+ * workspace queries are unchanged.
+ * ---------------------------------------------------------------------- */
+#define HHFM_TOPK_MAX_K 1024
+int hhfm_catalog_topk_wide_workspace(int64_t B, int32_t item_count, int32_t k,
+                                     int32_t K, size_t* ws_bytes);
 
 int hhfm_catalog_topk(const int32_t* qidx, int64_t B, int32_t ncols,
                       int32_t mode, int32_t user_col, int32_t ctx_begin,
@@ -512,6 +555,7 @@ int hhfm_pf_exclusion_lists(const int32_t* keys, int64_t nkeys, int32_t key_cols
  * multi-GPU path: RCCL all-gather output, rank-major).  Replaces the single
  * tf.nn.top_k over the full catalog (FM.py:185, OurModel7.py:295).
  *   in_score/in_idx: [R][B][K]; out_*: [B][K]; same (score desc, idx asc) order.
+ *   K <= HHFM_TOPK_MAX_K ("Wide K": K > 64 merges in LDS, one workgroup per query).
  * hhfm_topk_merge_host is the same merge on host memory (no GPU needed).
  * ---------------------------------------------------------------------- */
 int hhfm_topk_merge(const float* in_score, const int32_t* in_idx, int32_t R,
